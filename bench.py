@@ -11,11 +11,16 @@ all-reduce over RCCL when N > 1), SGD update.  Every step gets a different batch
 a fresh Geometry -- nothing is cached across steps.  K steps are timed between barrier + synchronize pairs; the MAX over
 ranks is reported; value = (points processed by all ranks) / time.
 
-The JSON line also carries
-  * "roofline": the dominant kernel's achieved algorithmic HBM GB/s (SURVEY.md 8d byte counts / HIP-event time of that
-    kernel measured live on the stream it runs on) against the 8 TB/s HBM3E peak;
+A plain run sets up, warms up, times the K steps and prints the line.  With --full the line also carries
+  * "kernels" / "roofline": per-call HIP-event times of the hot host calls (one step of the timed region carries the events)
+    and the dominant kernel's achieved algorithmic HBM GB/s (SURVEY.md 8d byte counts / that time) against the 8 TB/s HBM3E peak;
+  * "lookahead_sweep_ms_per_step", "eager_ms_per_step", "ddp_overhead_ms", "roofline_ops": runs of their own after the timed region;
   * "cpu_baseline": the CPU oracle (reference algorithms: brute-force kNN, iterative FPS, torch-CPU layers) timed on
-    this host's cores on a bounded sample of the same workload (rank 0, N = 1 only).
+    this host's cores on a bounded sample of the same workload (rank 0, N = 1 only);
+  * "efficiency_vs_n1" (N > 1 started without torchrun): against a one-rank run of the same command.
+
+--dump-outputs DIR writes what the last timed step computed (loss terms, per-point score, the updated parameters) as
+DIR/<name>.npy (float32, at most 64 MiB in all) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -119,8 +124,13 @@ def dense_flops_forward(n1, in_channels=6, num_classes=13, enc_bottlenecks=(1, 2
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=48)
-    ap.add_argument("--warmup", type=int, default=12)
+    ap.add_argument("--steps", type=int, default=48, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=12, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel HIP-event times and rooflines, the look-ahead / eager / "
+                         "gradient-exchange sweeps, the per-op roofline, the CPU baseline, the one-rank reference of N > 1 runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--throttle", action="store_true",
                     help="profiling aid: synchronise after every encoder / decoder block (forward and backward), so that at most ~100 "
                          "dispatches are in flight -- rocprofv3 --pmc serialises kernels and its interception dies ('AQL packet is "
@@ -145,8 +155,8 @@ def parse():
                     help="with --jitter: draw the scene sizes of a batch from this many fixed signatures (batch i has the sizes of class "
                          "i %% K) and give each class a captured graph of its own (engine.TrainStep(max_captures=K)); 0 = every batch its "
                          "own sizes (eager)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ops-roofline", action="store_true", help="skip the per-op HBM roofline micro-benchmark (rank 0, N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ops-roofline", action="store_true", help="with --full: skip the per-op HBM roofline micro-benchmark (rank 0, N = 1)")
     ap.add_argument("--cpu-points", type=int, default=100000, help="scene size of the bounded CPU-baseline sample")
     ap.add_argument("--st-group", type=int, default=3, help="--workload stratified: batches per grouped coordinate pre-pass (1 = one batch ahead)")
     ap.add_argument("--amp", nargs="?", const="f16", default=None, choices=["bf16", "f16"],
@@ -172,10 +182,10 @@ def parse():
                     help="gradient exchange for N > 1: one flat-buffer all-reduce after the backward (engine.FlatGradAllReduce) or "
                          "torch DistributedDataParallel (per-parameter bucket copies: +3 ms per step, measured)")
     ap.add_argument("--no-latency-sweep", action="store_true",
-                    help="skip the look-ahead sweep (serial step time with --prefetch 0 and groups of 1 / 2 / 3 batches; rank 0, N = 1)")
+                    help="with --full: skip the look-ahead sweep (serial step time with --prefetch 0 and groups of 1 / 2 / 3 batches; rank 0, N = 1)")
     ap.add_argument("--no-affinity", action="store_true", help="N > 1: do not pin each rank to its own contiguous share of the host's cores")
     ap.add_argument("--no-n1-reference", action="store_true",
-                    help="N > 1 started without torchrun: do not time the one-rank run that efficiency_vs_n1 is quoted against")
+                    help="with --full, N > 1 started without torchrun: do not time the one-rank run that efficiency_vs_n1 is quoted against")
     return ap.parse_args()
 
 
@@ -209,7 +219,7 @@ def launch_ranks(args):
         return max(abs(c) for c in codes), out
 
     n1 = None
-    if not args.no_n1_reference:
+    if args.full and not args.no_n1_reference:
         rc, out = run(1, ["--gpus", "1", "--no-cpu-baseline", "--no-ops-roofline", "--no-latency-sweep"])
         try:
             n1 = json.loads(out.strip().splitlines()[-1])
@@ -527,8 +537,33 @@ class TimedExchange:
         return (sum(a.elapsed_time(b) for a, b in self.events) / len(self.events)) if self.events else None
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, out, step, limit=DUMP_LIMIT_BYTES):
+    """What one training step hands its caller, as float32 .npy files: the loss terms and the per-point score of the returned dict,
+    and every parameter after the optimizer update (``parameters.npy``: step.parameters() flattened in order).  Arrays too large for
+    `limit` keep a fixed, seeded sample of their elements (sorted indices of numpy's default_rng(0), flattened), the smallest arrays
+    first; the sample depends only on the array's size, so two builds dump the same elements."""
+    import numpy as np
+
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items() if torch.is_tensor(v)}
+    arrays["parameters"] = torch.cat([p.detach().float().reshape(-1) for p in step.parameters()]).cpu().numpy()
+    budget = (limit - 4096 * len(arrays)) // 4   # (float32 elements, npy headers set aside)
+    os.makedirs(dirname, exist_ok=True)
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        keep = min(a.size, budget // (len(arrays) - i))
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        budget -= a.size
+        np.save(os.path.join(dirname, f"{name}.npy"), np.asarray(a, dtype=np.float32))
+    return sorted(arrays)
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args))
     from pointcloudpdf_amd import _native, engine, synthetic
@@ -591,7 +626,7 @@ def main():
     use_dp = world > 1 or force_dp
     module = engine.wrap_ddp(step, dev) if (use_dp and args.ddp == "torch") else step
     grad_sync = engine.FlatGradAllReduce(step) if (use_dp and args.ddp == "flat") else None
-    if grad_sync is not None and world > 1:
+    if grad_sync is not None and world > 1 and args.full:
         grad_sync = TimedExchange(grad_sync)
     if args.optimizer == "fused":   # one launch over all 304 tensors (csrc/optim.hip); "torch" = torch.optim.SGD(fused=True), 13 launches
         opt = engine.FusedSGD(step.parameters(), lr=1e-3, momentum=0.9, weight_decay=1e-4)
@@ -616,7 +651,8 @@ def main():
                   "window_attention_core", "window_attention_core_backward",   # (all of them + the softmax as one node: what the model calls)
                   "attention_step2_with_rel_pos_value_v2", "attention_step2_with_rel_pos_value_v2_backward"]
     timer = KernelTimer(be, names)
-    timer.install()
+    if args.full:   # (the per-call HIP events of the timed region's measuring step)
+        timer.install()
 
     amp_dtype = {None: None, "bf16": torch.bfloat16, "f16": torch.float16}[args.amp]
     # fp16 operands: the reference's AMP loop scales the loss dynamically (torch GradScaler, engines/train.py:343-355); here the same
@@ -723,8 +759,10 @@ def main():
 
     for rec in timer.records.values():
         rec.clear()
-    dt_local, out, sched = timed(args.prefetch, args.warmup, args.steps, with_timer=True)
+    dt_local, out, sched = timed(args.prefetch, args.warmup, args.steps, with_timer=args.full)
     D = sched.D
+    if args.dump_outputs and rank == 0:   # (before anything else runs a step: the replayed step's outputs are static buffers)
+        dump_outputs(args.dump_outputs, out, step)
     if st_prefetcher is not None:
         st_prefetcher.close()
     dt, rank_ms = dt_local, [dt_local / args.steps * 1e3]
@@ -741,8 +779,8 @@ def main():
         # same distribution, so the whole-job figure is this rank's count times the world size)
         pts_total = sum(pool_points[(args.warmup + i) % len(pool)] for i in range(args.steps)) * world
         pts_per_step = pts_total / args.steps
-        ks = timer.summary()
-        traffic, traffic_note = load_traffic()
+        ks = timer.summary()   # (empty without --full: no call carried events)
+        traffic, traffic_note = load_traffic() if args.full else ({}, None)
         if traffic and traffic.get("file"):
             traffic["file_date"] = time.strftime("%Y-%m-%d", time.gmtime(os.path.getmtime(os.path.join(ROOT, traffic["file"]))))
         steps_of = lambda name: args.steps if name in KernelTimer.ALWAYS else max(timer.sampled_steps, 1)
@@ -812,9 +850,11 @@ def main():
             "preflight": pre,
             "loss": loss,
             "execution": ("engine.GroupedGeometryLoader + engine.TrainStep: forward + backward replayed as one captured hipGraph (fixed scene sizes), "
-                          "optimizer / gradient exchange / geometry pre-pass eager; the ONE step of the timed region that carries per-kernel HIP events "
-                          + ("replays the segmented capture (engine.CapturedStep(split_calls=): graphs cut around the timed calls)" if getattr(sched, "segmented", False)
-                             else "runs eagerly" + (f" (segmented capture unavailable: {sched.instrument_error})" if getattr(sched, "instrument_error", None) else ""))
+                          "optimizer / gradient exchange / geometry pre-pass eager; "
+                          + (("the ONE step of the timed region that carries per-kernel HIP events "
+                              + ("replays the segmented capture (engine.CapturedStep(split_calls=): graphs cut around the timed calls)" if getattr(sched, "segmented", False)
+                                 else "runs eagerly" + (f" (segmented capture unavailable: {sched.instrument_error})" if getattr(sched, "instrument_error", None) else "")))
+                             if args.full else "every step of the timed region is a replay (no per-kernel HIP events without --full)")
                           if trainer.captured is not None else
                           ("engine.GroupedGeometryLoader + engine.TrainStep, eager (one Python-issued launch sequence per step)"
                            + (f"; graph capture failed: {trainer.capture_error}" if trainer.capture_error else ""))),
@@ -827,11 +867,10 @@ def main():
             "prepass_submit_host_ms": (1e3 * min(sched.submit_host_s)) if sched.submit_host_s else None,   # host time of one group submission (warm)
             # untimed, before the W warm-up steps: one throw-away group pre-pass per pre-pass stream (allocator pools at their steady state)
             "prepass_allocator_warmup_groups": sched_warm[0],
-            "kernels": ks,
-            "roofline": roof,
-            "roofline_gather_family": roof2,
         }
-        if not strat:
+        if args.full:
+            line.update(kernels=ks, roofline=roof, roofline_gather_family=roof2)
+        if args.full and not strat:
             # ---- matrix cores (north_star: "MFMA utilisation against peak"): the Linear layers' FLOPs of the step, 3 x forward (forward,
             # input gradient, weight gradient), against the dense peak of the operand type -- over the whole step (live), over
             # the time of the kernels that run them and as the matrix pipes' counter-measured busy share (builder-side SQ passes)
@@ -869,7 +908,7 @@ def main():
 
     # ---- latency: how much look-ahead the number above depends on (FPS is a serial chain per scene).  serial = pre-pass inline on
     # the main stream, every step pays the whole FPS chain; then groups of 1 / 2 / 3 batches.
-    if world == 1 and not args.no_latency_sweep and not args.pseudo_label and not strat:
+    if args.full and world == 1 and not args.no_latency_sweep and not args.pseudo_label and not strat:
         sweep = {}
         for Dl, st, wu in ((0, 4, 1), (1, 6, 2), (2, 6, 2), (3, 6, 3)):
             dtl, _, _ = timed(Dl, wu, st)
@@ -904,7 +943,7 @@ def main():
         line["lookahead_sweep_ms_per_step"] = sweep
 
     if rank == 0:
-        if world == 1 and not args.no_ops_roofline and not scannet and not strat:
+        if args.full and world == 1 and not args.no_ops_roofline and not scannet and not strat:
             # the pointops drop-in ops on their own (level-1 shapes of this config: 200k points, c = 32, k = 8), HIP-event timed on
             # the launching stream, against the 8 TB/s HBM peak with the SURVEY 8(d) byte counts (tools/ops_roofline.py)
             sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -921,7 +960,7 @@ def main():
                                              "pruning_factor_vs_bruteforce": round(r["pruning_factor"], 1)}
                                             if "pair_evals_per_s" in r else {}))
                                     for r in rows]
-        if world == 1 and not args.no_cpu_baseline and not scannet and not strat:   # (the CPU baseline is quoted on the headline workload)
+        if args.full and world == 1 and not args.no_cpu_baseline and not scannet and not strat:   # (the CPU baseline is quoted on the headline workload)
             line["cpu_baseline"] = cpu_baseline(args.cpu_points)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

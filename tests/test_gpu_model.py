@@ -245,7 +245,7 @@ def test_bench_launches_its_own_rccl_ranks():
         pytest.skip("needs two GPUs (the round-end scaling run has them; the 1-GPU test box does not)")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "4", "--points", "30000"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "4", "--points", "30000", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -266,7 +266,7 @@ def test_bench_two_rank_path_on_a_shared_gpu(launcher):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "4", "--points", "20000"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "4", "--points", "20000", "--full"]
     if launcher == "own":
         cmd = [sys.executable] + tail
     else:
@@ -287,6 +287,36 @@ def test_bench_two_rank_path_on_a_shared_gpu(launcher):
     assert abs(line["value"] - 2 * 2 * 20000 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
     assert abs(line["ms_per_step"] - max(line["rank_ms_per_step"])) <= 1e-9 and np.isfinite(line["loss"])
     assert ("efficiency_vs_n1" in line) == (launcher == "own")   # (the one-rank reference run belongs to bench.py's own launcher)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `python bench.py --gpus 1` run times exactly --steps steps and reports nothing that needs runs or events of its own
+    (those are --full's); --dump-outputs writes the last timed step's loss terms, score and updated parameters as float32 .npy files."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--points", "20000",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["n_gpus"] == 1 and line["higher_is_better"] is True
+    assert abs(line["value"] - 2 * 20000 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for key in ("roofline", "kernels", "cpu_baseline", "roofline_ops", "lookahead_sweep_ms_per_step", "eager_ms_per_step", "mfma"):
+        assert key not in line, key
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["loss.npy", "model_loss.npy", "parameters.npy", "recognizer_loss.npy", "score.npy"], files
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 * 2 ** 20
+    assert arrays["score"].shape == (2 * 20000,) and abs(float(arrays["loss"]) - line["loss"]) <= 1e-6 * abs(line["loss"])
+    from pointcloudpdf_amd import engine
+
+    assert arrays["parameters"].size == sum(p.numel() for p in engine.OpenSegStep().parameters())
 
 
 def test_captured_step_replays_the_eager_step():

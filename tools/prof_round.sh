@@ -4,7 +4,8 @@
 TAG=${1:-r02_a}
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $R/gpurun_out/${TAG}_bench.json 2> $R/gpurun_out/${TAG}_bench.err
+mkdir -p $R/bench_out   # (the bench line with every figure of --full)
+python3 $R/bench.py --full > $R/bench_out/${TAG}_bench.json 2> $R/bench_out/${TAG}_bench.err
 rocprofv3 --kernel-trace --stats -d /tmp/p/kt -o kt -- python3 $R/bench.py --steps 12 --warmup 6 --no-cpu-baseline --no-ops-roofline --no-latency-sweep > $R/gpurun_out/${TAG}_kt_bench.log 2>&1
 DB=$(find /tmp/p/kt -name "*.db" | head -1)
 python3 $R/tools/rocpd_stats.py $DB 70 > $R/gpurun_out/${TAG}_kernel_trace_stats.txt
