@@ -372,6 +372,19 @@ int pdf_ce_forward(long n, int c, const float *logits, const long *target, long 
                    void *stream);
 int pdf_ce_backward(long n, int c, const float *dlogits, const float *acc, const float *gy, float *grad_out, void *stream);
 
+/* Distillation loss of the incremental learner (pointcept/incrLearners/ours/pointpdf_incr_v1m1_base.py:62-87, IncrDistillKlLoss):
+ * student (n, cs) and teacher (n, ct) fp32 logits, labels (n) int64, ct <= cs <= 64.  Target row t = [softmax(teacher * inv_tt), 0 ..]
+ * padded to cs columns, or onehot(label) where label != ignore; loss[0] = sum_rows sum_j (xlogy(t_j, t_j) - t_j log_softmax(student *
+ * inv_tp)_j) / n (kl_div "batchmean": divided by ALL n rows).  grad (n*cs) receives softmax(student * inv_tp) * sum_j t_j - t; acc
+ * (pdf_incr_kl_workspace_floats() floats) receives [sum, inv_tp / n] in its first two floats, the rest per-workgroup partial sums added
+ * in a fixed order (no atomics, nothing to zero, bit-reproducible).  A label that is neither `ignore` nor in [0, cs) makes the loss NaN
+ * (its row's gradient is 0).  n < 1, ct < 1 or ct > cs: PDF_ERR_BAD_ARG; cs > 64: PDF_ERR_UNSUPPORTED.  Backward: grad_out = dgrad *
+ * gy[0] * inv_tp / n; dgrad (the forward's `grad`) is only read, so the node can be differentiated more than once. */
+long pdf_incr_kl_workspace_floats(void);
+int pdf_incr_kl_forward(long n, int cs, int ct, const float *student, const float *teacher, const long *labels, long ignore, float inv_tp,
+                        float inv_tt, float *grad, float *acc, float *loss, void *stream);
+int pdf_incr_kl_backward(long n, int cs, const float *dgrad, const float *acc, const float *gy, float *grad_out, void *stream);
+
 /* Per-scene sums of the relative coordinates rel = xyz[idx[i, j]] - xyz[i] of a SELF neighbour table (rows with idx < 0: rel = 0):
  * out (b, 9) double = [Sx Sy Sz | Mxx Mxy Mxz Myy Myz Mzz], WRITTEN (every workgroup lies inside one scene and stores its nine sums
  * into its own slot of ws -- pdf_knn_rel_moments_ws_doubles(b, n) doubles --, a second launch adds a scene's slots in order: no

@@ -658,6 +658,13 @@ class HipBackend(CBackend):
         lib.pdf_ce_forward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_ce_backward.restype = c_int
         lib.pdf_ce_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.pdf_incr_kl_workspace_floats.restype = c_long
+        lib.pdf_incr_kl_workspace_floats.argtypes = []
+        lib.pdf_incr_kl_forward.restype = c_int
+        lib.pdf_incr_kl_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, ctypes.c_float, ctypes.c_float,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.pdf_incr_kl_backward.restype = c_int
+        lib.pdf_incr_kl_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_knn_rel_moments.restype = c_int
         lib.pdf_knn_rel_moments.argtypes = [c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_knn_rel_moments_ws_doubles.restype = c_long

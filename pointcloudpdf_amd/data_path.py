@@ -10,6 +10,8 @@ With GridSample (voxelize.py) this closes the per-batch input pipeline voxelise 
   of the kept points, "random" / "center" centre choice, scenes at or below ``point_max`` left untouched) is reproduced.
 * ``collate_fn`` / ``point_collate_fn`` are upstream's recursion (tensors concatenated, every key containing "offset" turned into
   cumulative ends, Mix3D merge of neighbouring scenes).
+* ``mask_label`` / ``remap_label`` are ``MaskLabel`` / ``RemapLabel`` (transform.py:1145-1206) of the incremental stage on device
+  label tensors: lookup-table gathers, no host read (the table is sized by the remapped keys, not by ``segment.max()``).
 Plumbing on torch device ops; the arithmetic is a three-term fp32 sum per point -- nothing here is worth a hand-written kernel.
 """
 import random
@@ -93,3 +95,47 @@ def point_collate_fn(batch, mix_prob=0):
             batch["offset_ori"] = batch["offset"].clone()
             batch["offset"] = torch.cat([batch["offset"][1:-1:2], batch["offset"][-1].unsqueeze(0)], dim=0)
     return batch
+
+
+def _lookup(segment, table, outside):
+    """table[segment] where 0 <= segment < len(table), ``outside`` (a tensor like ``segment`` or a scalar) elsewhere."""
+    table = table.to(segment.device, non_blocking=True)
+    inside = (segment >= 0) & (segment < table.numel())
+    return torch.where(inside, table[segment.clamp(0, table.numel() - 1)], outside)
+
+
+def mask_label(segment, mask_label=None, mask_to=-1):
+    """transform.py:1145-1158 -> ``segment_known``: the labels in ``mask_label`` become ``mask_to``; ``segment`` itself is untouched."""
+    if mask_label is None:
+        return segment.clone()
+    labels = [int(v) for v in mask_label]
+    if not labels:
+        return segment.clone()
+    hit = [False] * (max(labels) + 1)
+    for v in labels:
+        if v >= 0:
+            hit[v] = True
+    masked = _lookup(segment, torch.tensor(hit), torch.zeros((), dtype=torch.bool, device=segment.device))
+    return torch.where(masked, torch.full_like(segment, mask_to), segment)
+
+
+def remap_label(segment, remap_dict, remap_select=None, ignore_index=-1):
+    """transform.py:1161-1206 -> (``segment_incr_remap``, ``segment_incr``).  ``segment_incr_remap``: every key of ``remap_dict`` replaced by
+    its new label, every other label kept; ``segment_incr``: the new label on the remapped points, ``ignore_index`` everywhere else (the
+    distillation target's "labelled" rows).  With ``remap_select``, only the selected keys are remapped; the unselected keys become
+    ``ignore_index`` in both outputs (:1177-1191).  Labels outside [0, max key] take the identity / ``ignore_index`` entries as well; the
+    reference's numpy table would wrap a negative label around to its last entry (no S3DIS label is negative)."""
+    keys = [int(k) for k in remap_dict]
+    size = max(keys) + 1
+    remap, inc = list(range(size)), [ignore_index] * size
+    if remap_select is not None:
+        selected = set(int(k) for k in remap_select)
+        for k in keys:
+            new = int(remap_dict[k]) if k in selected else ignore_index
+            remap[k] = inc[k] = new
+    else:
+        for k in keys:
+            remap[k] = inc[k] = int(remap_dict[k])
+    segment_incr_remap = _lookup(segment, torch.tensor(remap, dtype=segment.dtype), segment)
+    segment_incr = _lookup(segment, torch.tensor(inc, dtype=segment.dtype), torch.full_like(segment, ignore_index))
+    return segment_incr_remap, segment_incr

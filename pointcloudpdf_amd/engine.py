@@ -83,11 +83,66 @@ class OpenSegStep(nn.Module):
                     score=rec["score"].detach())
 
 
+class IncrSegStep(nn.Module):
+    """One step of the incremental stage -- ``IncrSegTrainer.model_forward`` (engines/train.py:502-560): the frozen base model (the
+    teacher, ``DefaultSegmentor`` with a ``num_classes`` head) and ``PointPdf-incr-v1m1`` (the student, a ``num_classes +
+    len(incr_label_remap)`` head) on the same batch; the loss is the distillation loss against ``segment_incr`` (incremental.py).
+
+    * The teacher's parameters do not require gradients (only the student's reach ``TrainStep`` / ``FusedSGD`` / ``FlatGradAllReduce``),
+      and the teacher stays in eval mode when the step is put in ``.train()`` (``before_epoch``, train.py:512-517): its BatchNorm uses
+      running statistics and its forward runs under no_grad on the fused eval-mode path.
+    * Teacher and student receive the same input dict, so one ``pdf_geometry`` (the look-ahead pre-pass, or the one the student's forward
+      builds) serves both networks.
+    * ``batch_keys``: the batch tensors a ``CapturedStep`` keeps at fixed addresses (``segment_incr`` instead of ``segment``); the loss is
+      one sync-free kernel per direction, so the whole step -- teacher forward included -- replays as one graph."""
+
+    batch_keys = ("coord", "feat", "offset", "segment_incr")
+
+    def __init__(self, backbone="PointTransformer-Seg50", in_channels=6, num_classes=13, incr_label_remap=None, pred_temp=1.0,
+                 target_temp=1.0, loss_weight=1.0):
+        super().__init__()
+        from . import incremental
+        from .registry import INCREMENTALLEARNER
+
+        remap = {5: 13, 9: 14} if incr_label_remap is None else dict(incr_label_remap)
+        ce = [dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1)]
+        teacher = MODELS.build(dict(type="DefaultSegmentor", backbone=dict(type=backbone, in_channels=in_channels, num_classes=num_classes),
+                                    criteria=ce))
+        teacher.requires_grad_(False)
+        self.learner = INCREMENTALLEARNER.build(dict(type="PointPdf-incr-v1m1", eval_criteria=ce,
+                                                     backbone=dict(type=backbone, in_channels=in_channels, num_classes=num_classes + len(remap))))
+        self.learner.criteria = incremental.IncrDistillKlLoss(pred_temp, target_temp, loss_weight)
+        self.learner.inject_teacher_model(teacher)
+        self.incr_label_remap = remap
+        self.train()
+
+    @property
+    def teacher(self):
+        return self.learner.teacher_model
+
+    @property
+    def student(self):
+        return self.learner.incr_backbone
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.teacher.eval()
+        return self
+
+    def forward(self, batch):
+        input_dict = dict(batch)
+        with dense.deferred_counters():   # BatchNorm step counters: one multi-tensor add per step
+            return self.learner(input_dict)
+
+
 def release_autograd_state(step):
     """Drop every reference an ``OpenSegStep`` keeps to the last step's autograd graph (the hook tap's captured tensors).  A live graph
     keeps its AccumulateGrad nodes -- and the stream they were created on -- alive; needed before a step is captured into a hipGraph on
-    another stream (``CapturedStep``), harmless otherwise."""
-    for per_module in step.hooks.output.values():
+    another stream (``CapturedStep``), harmless otherwise.  (A step module without a hook tap -- ``IncrSegStep`` -- keeps none.)"""
+    hooks = getattr(step, "hooks", None)
+    if hooks is None:
+        return
+    for per_module in hooks.output.values():
         for key in per_module:
             per_module[key] = None
 
@@ -130,7 +185,7 @@ class CapturedStep:
     are the graph's own static tensors (re-bound after every replay, so an eager step in between does no harm).  Python-side scalars
     of the step (``PointPdfV1.alpha``, ``epoch`` gates, BatchNorm momenta) are baked in at capture: re-capture when they change."""
 
-    KEYS = ("coord", "feat", "offset", "segment")
+    KEYS = ("coord", "feat", "offset", "segment")   # a step module may name other batch tensors in ``batch_keys`` (IncrSegStep)
 
     def __init__(self, step, batch, geom=None, warmup=2, autocast=None, loss_scale=1.0, stream=None, debug_graph=False, split_calls=None,
                  describe=None):
@@ -158,7 +213,8 @@ class CapturedStep:
         self.step = step
         dev = batch["coord"].device
         self.sizes = [int(v) for v in batch["offset_host"]]
-        self.static = {k: batch[k].clone() for k in self.KEYS}
+        self.keys = tuple(getattr(step, "batch_keys", self.KEYS))
+        self.static = {k: batch[k].clone() for k in self.keys}
         self.static["offset_host"] = list(self.sizes)
         if geom is None:
             geom = Geometry(batch["coord"], batch["offset"], batch["offset_host"]).precompute()
@@ -365,7 +421,7 @@ class CapturedStep:
         """True when the captured graph IS this step: same scene sizes / shapes and the same Python-side schedule state as at capture.
         (A graph replays what was recorded: after ``PointPdfV1.trigger_operation`` moved ``alpha`` or an epoch gate opened, or after
         ``step.eval()``, the caller must run the eager step or capture again -- ``__call__`` refuses a stale graph.)"""
-        return ([int(v) for v in batch["offset_host"]] == self.sizes and all(batch[k].shape == self.static[k].shape for k in self.KEYS)
+        return ([int(v) for v in batch["offset_host"]] == self.sizes and all(batch[k].shape == self.static[k].shape for k in self.keys)
                 and self._python_state() == self.frozen)
 
     @torch.no_grad()
@@ -380,7 +436,7 @@ class CapturedStep:
             raise RuntimeError("CapturedStep: the step's Python-side state (recognizer alpha / epoch gate / step_loss_weight / train mode / "
                                f"autocast) changed since the capture: {self.frozen} -> {self._python_state()}; capture again "
                                "(CapturedStep(step, batch, ...)) or run the eager step")
-        self.geometry.stage(geom, extra=[(batch[k], self.static[k]) for k in self.KEYS])
+        self.geometry.stage(geom, extra=[(batch[k], self.static[k]) for k in self.keys])
         if self.segments is not None:
             for g, label, info in self.segments:
                 if label is not None and on_call is not None:

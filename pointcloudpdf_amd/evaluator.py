@@ -97,3 +97,64 @@ class OpenSegEvaluator:
                     aupr=float(np.mean(self.aupr)) if self.aupr else float("nan"),
                     auroc=float(np.mean(self.auroc)) if self.auroc else float("nan"),
                     loss=float(np.mean(self.losses)) if self.losses else float("nan"))
+
+
+def _selected(labels, k):
+    """utils/misc.py:184-187 (``selected_mask``)."""
+    m = np.zeros(k, dtype=bool)
+    m[list(labels)] = True
+    return m
+
+
+class IncrSegEvaluator:
+    """What ``IncrSegEvaluator.eval`` logs for the incremental stage (engines/hooks/evaluator.py:233-405): class histograms of the
+    incremental learner's arg-max against ``segment_incr_remap`` over K = base + len(remap) classes, summarised over three class sets:
+    ``known`` (the base classes that were not remapped), ``incr`` (the new ids of the selected remapped classes) and ``remap`` (all classes
+    except the old and new ids of the remapped ones, plus the selected new ids) -- the masks of :237-261 and :377-405."""
+
+    def __init__(self, base_num_classes, incr_label_remap, incr_label_select=None, ignore_index=-1):
+        remap = {int(k): int(v) for k, v in incr_label_remap.items()}
+        select = list(remap) if incr_label_select is None else [int(k) for k in incr_label_select]
+        self.base_num_classes, self.ignore_index = int(base_num_classes), ignore_index
+        self.num_classes = self.base_num_classes + len(remap)
+        self.mask_known = ~_selected(list(remap), self.base_num_classes)
+        self.incr_label_idx = [remap[k] for k in select if k in remap]
+        self.mask_incr_remap = ~_selected(list(remap) + list(remap.values()), self.num_classes) | _selected(self.incr_label_idx, self.num_classes)
+        self.map_reverse = {v: k for k, v in remap.items()}
+        self.reset()
+
+    def reset(self):
+        self.hist = None   # (3, K) float64 on the device: intersection | union | target
+        self.losses = []
+
+    @torch.no_grad()
+    def update(self, seg_logits, segment_incr_remap, loss=None):
+        pred = seg_logits.max(1)[1]
+        i, u, t = intersection_and_union(pred, segment_incr_remap, self.num_classes, self.ignore_index)
+        h = torch.stack([i, u, t]).double()
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.all_reduce(h)
+        self.hist = h if self.hist is None else self.hist + h
+        if loss is not None:
+            self.losses.append(float(loss))
+
+    def metrics(self, intersection, union, target):
+        """``incr_segmentation_metric`` (:377-405) over host arrays -> (iou_class, acc_class, known, incr, remap)."""
+        iou_class = intersection / (union + 1e-10)
+        acc_class = intersection / (target + 1e-10)
+        b, k, idx, r = self.base_num_classes, self.mask_known, self.incr_label_idx, self.mask_incr_remap
+        known = {"mIoU": np.mean(iou_class[:b][k]), "mAcc": np.mean(acc_class[:b][k]),
+                 "Acc": sum(intersection[:b][k]) / sum(target[:b][k] + 1e-10)}
+        incr = {"mIoU": np.mean(iou_class[idx]), "mAcc": np.mean(acc_class[idx]), "Acc": sum(intersection[idx]) / (sum(target[idx]) + 1e-10)}
+        remap = {"mIoU": np.mean(iou_class[r]), "mAcc": np.mean(acc_class[r]), "Acc": sum(intersection[r]) / (sum(target[r]) + 1e-10)}
+        return iou_class, acc_class, known, incr, remap
+
+    def summary(self):
+        inter, union, target = (self.hist[j].cpu().numpy() for j in range(3))
+        iou_class, acc_class, known, incr, remap = self.metrics(inter, union, target)
+        out = dict(iou_class=iou_class, acc_class=acc_class, known=known, incr=incr, remap=remap,
+                   loss=float(np.mean(self.losses)) if self.losses else float("nan"))
+        for name, m in (("known", known), ("incr", incr), ("remap", remap)):
+            for key, v in m.items():
+                out[f"{key}_{name}"] = float(v)
+        return out

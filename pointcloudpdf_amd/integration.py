@@ -31,6 +31,14 @@ def register_into_pointcept(force=True):
     except ImportError:
         pass
     try:
+        from pointcept.incrLearners.builder import INCREMENTALLEARNER as PC_INCR
+        from . import incremental  # noqa: F401  (fills the registry)
+        from .registry import INCREMENTALLEARNER
+
+        PC_INCR.register_module(name="PointPdf-incr-v1m1", force=force, module=INCREMENTALLEARNER.get("PointPdf-incr-v1m1"))
+    except ImportError:
+        pass
+    try:
         from pointcept.models.utils.model_hook import MODELHOOKS as PC_HOOKS
 
         PC_HOOKS.register_module(name="ModelHook", force=force, module=MODELHOOKS.get("ModelHook"))

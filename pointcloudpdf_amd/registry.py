@@ -73,6 +73,7 @@ MODELS = Registry("models")
 LOSSES = Registry("losses")
 RECOGNIZER = Registry("recognizer")
 MODELHOOKS = Registry("modelhook")
+INCREMENTALLEARNER = Registry("incremental_learner")
 
 
 def build_model(cfg):
