@@ -464,6 +464,37 @@ int pdf_attention_step2_with_rel_pos_value_backward_v2_l(int N, int M, int h, in
  * division (NumPy >= 2 promotion), f32 = 1: float32 division (NumPy 1.x). */
 int pdf_grid_hash(long n, int b, const float *coord, const int *offset, double gx, double gy, double gz, int f32,
                   const long long *min_grid, long long *grid, unsigned long long *key, void *stream);
+/* The same on float64 coordinates (S3DIS stores them as float64; RandomRotate promotes float32 ones): floor(coord / grid) in float64. */
+int pdf_grid_hash_f64(long n, int b, const double *coord, const int *offset, double gx, double gy, double gz,
+                      const long long *min_grid, long long *grid, unsigned long long *key, void *stream);
+
+/* ---- training augmentation of raw scenes (csrc/augment.hip; pointcept/datasets/transform.py, the PDF configs' train lists).
+ * pdf_philox4x64: out (n,4) = Philox4x64-10 blocks for key (key0, key1), counters ctr0 .. ctr0 + n - 1 (word 0; carry into word 1);
+ *   numpy.random.Philox(counter=c, key=k).random_raw(4) is the block of counter c + 1.
+ * pdf_aug_bounds: per-scene min / max of coord (n,3) f64 [and color (n,3) f64, may be NULL] -> bounds (b,12): coord min, coord max,
+ *   colour min, colour max.  offset (b + 1) int64 scene starts; part: pdf_aug_bounds_workspace_doubles(b) doubles.  No atomics.
+ * pdf_aug_points: one segment of `nop` ops on every point, in place on fp64 rows (coord, color, normal; color / normal may be NULL).
+ *   table (b, 1 + nop, 16) f64: row 0 = the scene's 64-bit key (bit pattern), rows 1.. = op code, fired flag, parameters and the
+ *   scene's current NumPy dtype per array (pointcloudpdf_amd/augment.py builds it); bounds (b,12) of the segment's start (may be NULL
+ *   when no op reads it); rec (k, n, 3) f64 recorded per-point normals (may be NULL: drawn in the kernel).
+ * pdf_aug_keys: out (n) uint64 = word 0 of the Philox block (scene_keys[s], stream_id; counter = index in the scene). */
+int pdf_philox4x64(long n, long key0, long key1, long ctr0, unsigned long long *out, void *stream);
+int pdf_aug_bounds_workspace_doubles(int b);
+int pdf_aug_bounds(int b, const long long *offset, const double *coord, const double *color, double *part, double *bounds, void *stream);
+int pdf_aug_points(int b, long n, const long long *offset, int nop, const double *table, const double *bounds, const double *rec,
+                   double *coord, double *color, double *normal, void *stream);
+int pdf_aug_keys(int b, long n, const long long *offset, const unsigned long long *scene_keys, long stream_id, unsigned long long *out,
+                 void *stream);
+/* ElasticDistortion, one (granularity, magnitude) stage.  vinfo (int64): voxel starts (b + 1) of the scenes' noise volumes, dims (b,3),
+ * axis starts (b + 1); vol (total, 3) float32 C-order volumes.  pdf_aug_elastic_noise: standard normals (Philox, as pdf_aug_keys;
+ * counter = voxel index in the scene).  pdf_aug_elastic_blur: one 3-tap 1/3 box pass along `axis` with zero boundary, in != out.
+ * pdf_aug_elastic_apply: coord += trilinear sample of vol on the scene's axes (f64, zero outside) * magnitude, rounded to the scene's
+ * dtype; params (b,2) f64 = fired, float32 flag; disp (n,3) f64 may be NULL (receives the sample). */
+int pdf_aug_elastic_noise(int b, long total, const long long *vinfo, const unsigned long long *scene_keys, long stream_id, float *vol,
+                          void *stream);
+int pdf_aug_elastic_blur(int b, long total, const long long *vinfo, const float *in, float *out, int axis, void *stream);
+int pdf_aug_elastic_apply(int b, long n, const long long *offset, const long long *vinfo, const double *axes, const float *vol,
+                          const double *params, double magnitude, double *coord, double *disp, void *stream);
 
 /* ---- test-time fragment voting (pointcept/engines/test.py:218-229, 243-251): pred[index[r], :] +=
  * softmax(logits[r, :]); score_sum[index[r]] += score[r]; score_cnt[index[r]] += 1.  index (n) int64, distinct within a call

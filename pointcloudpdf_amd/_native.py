@@ -64,6 +64,14 @@ _PROTOS = {
 }
 _HIP_ONLY_PROTOS = {
     "grid_hash": "lippdddippp",
+    "grid_hash_f64": "lippdddppp",
+    "philox4x64": "llllp",
+    "aug_bounds": "ippppp",
+    "aug_points": "ilpipppppp",
+    "aug_keys": "ilpplp",
+    "aug_elastic_noise": "ilpplp",
+    "aug_elastic_blur": "ilpppi",
+    "aug_elastic_apply": "ilpppppdpp",
     "radius_neighbors_self": "iifppipppl",
     "vote_accumulate": "lipppppp",
     "graph_forest": "lipppppipppl",
@@ -627,6 +635,8 @@ class HipBackend(CBackend):
         lib.pdf_fps_stats_offset.argtypes = [c_int, c_int]
         self.collect_fps_stats = False  # debug: keep the work counters of the last bucketed FPS call (forces a sync)
         self.last_fps_stats = None
+        lib.pdf_aug_bounds_workspace_doubles.restype = c_int
+        lib.pdf_aug_bounds_workspace_doubles.argtypes = [c_int]
         lib.pdf_abi_version.restype = c_int
         lib.pdf_build_info.restype = ctypes.c_char_p
         got = int(lib.pdf_abi_version())
@@ -1604,6 +1614,115 @@ class HipBackend(CBackend):
         gx, gy, gz = (float(g) for g in grid_size)
         self._call("grid_hash", n, offset.shape[0], coord, offset, gx, gy, gz, 1 if float32_division else 0, min_grid, grid, key)
         return grid, key
+
+    def grid_hash_f64(self, coord, offset, grid_size, min_grid):
+        """grid_hash on float64 coordinates (csrc/augment.hip): floor(coord / grid_size) in float64, as the reference divides S3DIS's
+        float64 coordinates and RandomRotate's promoted ones."""
+        _check(coord, torch.float64, "coord"); _check(offset, torch.int32, "offset"); _check(min_grid, torch.int64, "min_grid")
+        n = coord.shape[0]
+        if coord.dim() != 2 or coord.shape[1] != 3 or min_grid.shape != (offset.shape[0], 3):
+            raise ValueError("grid_hash_f64: coord (n,3), min_grid (b,3)")
+        grid = self._new(coord, (n, 3), torch.int64)
+        key = self._new(coord, (n,), torch.int64)
+        gx, gy, gz = (float(g) for g in grid_size)
+        self._call("grid_hash_f64", n, offset.shape[0], coord, offset, gx, gy, gz, min_grid, grid, key)
+        return grid, key
+
+    # -- training augmentation (csrc/augment.hip; pointcloudpdf_amd/augment.py drives them) ------------------------------------------
+    @staticmethod
+    def _i64(v):
+        v = int(v) & ((1 << 64) - 1)
+        return v - (1 << 64) if v >= 1 << 63 else v
+
+    def philox4x64(self, n, key, ctr0, device):
+        """(n, 4) int64 holding the uint64 words of Philox4x64-10 blocks for key (128-bit int) and counters ctr0 .. ctr0 + n - 1."""
+        if n < 0:
+            raise ValueError("philox4x64: n >= 0")
+        out = torch.empty((int(n), 4), dtype=torch.int64, device=device)
+        self._call("philox4x64", int(n), self._i64(key), self._i64(int(key) >> 64), self._i64(ctr0), out)
+        return out
+
+    def _aug_rows(self, offset, n, *rows):
+        _check(offset, torch.int64, "offset")
+        if offset.dim() != 1 or offset.shape[0] < 2:
+            raise ValueError("offset: (b + 1) int64 scene starts")
+        for name, t in rows:
+            if t is not None:
+                _check(t, torch.float64, name)
+                if t.shape != (n, 3):
+                    raise ValueError(f"{name}: expected ({n}, 3), got {tuple(t.shape)}")
+
+    def aug_bounds(self, offset, coord, color=None):
+        """-> (b, 12) float64 per-scene coord min, coord max, colour min, colour max.  offset (b + 1) int64 scene starts."""
+        n = coord.shape[0]
+        self._aug_rows(offset, n, ("coord", coord), ("color", color))
+        b = offset.shape[0] - 1
+        part = self._new(coord, (max(int(self.lib.pdf_aug_bounds_workspace_doubles(b)), 1),), torch.float64)
+        bounds = self._new(coord, (b, 12), torch.float64)
+        self._call("aug_bounds", b, offset, coord, color if color is not None else ctypes.c_void_p(None), part, bounds)
+        return bounds
+
+    def aug_points(self, offset, table, bounds, rec, coord, color=None, normal=None):
+        """One segment of the transform list, in place on the fp64 rows.  table (b, 1 + nop, 16) float64 (augment.py: _Program)."""
+        n = coord.shape[0]
+        self._aug_rows(offset, n, ("coord", coord), ("color", color), ("normal", normal))
+        b = offset.shape[0] - 1
+        _check(table, torch.float64, "table")
+        if table.dim() != 3 or table.shape[0] != b or table.shape[2] != 16 or table.shape[1] < 1:
+            raise ValueError("table: (b, 1 + nop, 16) float64")
+        if bounds is not None:
+            _check(bounds, torch.float64, "bounds")
+            if bounds.shape != (b, 12):
+                raise ValueError("bounds: (b, 12)")
+        if rec is not None:
+            _check(rec, torch.float64, "rec")
+            if rec.dim() != 3 or rec.shape[1:] != (n, 3):
+                raise ValueError("rec: (k, n, 3) float64")
+        nul = ctypes.c_void_p(None)
+        self._call("aug_points", b, n, offset, table.shape[1] - 1, table, nul if bounds is None else bounds, nul if rec is None else rec,
+                   coord, nul if color is None else color, nul if normal is None else normal)
+
+    def aug_keys(self, offset, n, scene_keys, stream_id):
+        """-> (n) int64 holding one uint64 Philox key per point (scene key, stream id; counter = index in the scene).
+        offset (b + 1) int64 scene starts with offset[-1] == n (the caller's host copy of the sizes gives n)."""
+        _check(offset, torch.int64, "offset"); _check(scene_keys, torch.int64, "scene_keys")
+        if offset.dim() != 1 or offset.shape[0] < 2 or scene_keys.shape != (offset.shape[0] - 1,) or n < 0:
+            raise ValueError("aug_keys: offset (b + 1) int64, scene_keys (b,) int64, n >= 0")
+        out = self._new(scene_keys, (int(n),), torch.int64)
+        self._call("aug_keys", offset.shape[0] - 1, int(n), offset, scene_keys, self._i64(stream_id), out)
+        return out
+
+    def aug_elastic_stage(self, offset, coord, vinfo, total, axes, params, magnitude, scene_keys, stream_id, noise=None, keep_disp=False):
+        """One ElasticDistortion stage in place on coord (n,3) f64: noise volume (``noise`` (total,3) float32 recorded, or drawn), two
+        rounds of the x / y / z box blur, trilinear sampling.  vinfo (5b + 2) int64: voxel starts, dims (b,3), axis starts; axes f64;
+        params (b,2) f64 (fired, float32 flag).  -> (blurred volume (total,3) float32, displacement (n,3) f64 or None)."""
+        n = coord.shape[0]
+        self._aug_rows(offset, n, ("coord", coord))
+        b = offset.shape[0] - 1
+        _check(vinfo, torch.int64, "vinfo"); _check(axes, torch.float64, "axes"); _check(params, torch.float64, "params")
+        _check(scene_keys, torch.int64, "scene_keys")
+        if vinfo.shape != (5 * b + 2,) or params.shape != (b, 2) or scene_keys.shape != (b,) or total < 0:
+            raise ValueError("aug_elastic_stage: vinfo (5b + 2), params (b, 2), scene_keys (b,)")
+        vh = vinfo.cpu() if vinfo.is_cuda else vinfo
+        if int(vh[b]) != total or axes.shape[0] != int(vh[4 * b + 1 + b]) or bool((vh[b + 1:4 * b + 1] < 0).any()):
+            raise ValueError("aug_elastic_stage: vinfo disagrees with total / axes")
+        a = self._new(coord, (max(total, 1), 3), torch.float32)
+        if noise is not None:
+            _check(noise, torch.float32, "noise")
+            if noise.shape != (total, 3):
+                raise ValueError(f"noise: expected ({total}, 3)")
+            a[:total].copy_(noise)
+        else:
+            self._call("aug_elastic_noise", b, int(total), vinfo, scene_keys, self._i64(stream_id), a)
+        t = self._new(coord, (max(total, 1), 3), torch.float32)
+        for _ in range(2):
+            for axis in range(3):
+                self._call("aug_elastic_blur", b, int(total), vinfo, a, t, axis)
+                a, t = t, a
+        disp = self._new(coord, (n, 3), torch.float64, zero=True) if keep_disp else None
+        self._call("aug_elastic_apply", b, n, offset, vinfo, axes, a, params, float(magnitude), coord,
+                   disp if disp is not None else ctypes.c_void_p(None))
+        return a[:total], disp
 
     def vote_accumulate(self, logits, score, index, pred, score_sum, score_cnt):
         """One test-time fragment into the running vote (engines/test.py:218-229, 243-251); index entries must be distinct."""

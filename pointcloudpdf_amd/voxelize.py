@@ -20,7 +20,7 @@ _SIGN = -(2 ** 63)
 
 
 def grid_sample(coord, offset, grid_size, mode="train", generator=None, float32_division=False, offset_host=None):
-    """coord (N,3) f32 (device), offset (B) cumulative ends ->  dict with
+    """coord (N,3) f32 or f64 (device; f64 goes through pdf_grid_hash_f64), offset (B) cumulative ends ->  dict with
          key (N) int64 (uint64 FNV key bits), grid_coord (N,3) int64 scene-relative, order (N) point ids scene-major / key-sorted,
          inverse (N) voxel id of every point (per-scene numbering like upstream: rank among the scene's sorted unique keys),
          count (V) points per voxel, voxel_offset (B) cumulative voxel counts,
@@ -35,7 +35,12 @@ def grid_sample(coord, offset, grid_size, mode="train", generator=None, float32_
     mins = torch.stack([coord[s:e].amin(0) if e > s else coord.new_zeros(3) for s, e in zip(starts, ends)])   # (B,3)
     g = torch.tensor(gs, dtype=torch.float32 if float32_division else torch.float64, device=coord.device)
     min_grid = torch.floor(mins.to(g.dtype) / g).long().contiguous()          # floor is monotone: = min over the scene of floor(c / g)
-    grid, key = be.grid_hash(coord.contiguous(), offset.int().contiguous(), gs, min_grid, float32_division)
+    if coord.dtype == torch.float64:                     # S3DIS coordinates, or float32 ones RandomRotate promoted
+        if float32_division:
+            raise ValueError("grid_sample: float32_division applies to float32 coordinates only")
+        grid, key = be.grid_hash_f64(coord.contiguous(), offset.int().contiguous(), gs, min_grid)
+    else:
+        grid, key = be.grid_hash(coord.contiguous(), offset.int().contiguous(), gs, min_grid, float32_division)
     scene = torch.bucketize(torch.arange(n, device=coord.device), offset.long(), right=True)
     skey = key ^ _SIGN                                   # unsigned order under a signed sort
     o1 = torch.sort(skey, stable=True)[1]
