@@ -39,8 +39,9 @@ extern "C" {
  * version must refuse to call (parameter lists differ; pointcloudpdf_amd/_native.py does).  History: 1 = rounds 1-3 (signatures changed
  * without a bump, see ADVICE of round 3); 4 = round 4: `mma_input` per call on the pdf_rowlin_ / pdf_block_ / pdf_bottleneck_ / pdf_linbn_ /
  * pdf_td_ entries, pdf_set_mma_input / pdf_get_mma_input / pdf_tickets_* removed, pdf_sgd_step takes a found-inf flag;
- * 5 = round 5: pdf_wa_* (atomic-free window-attention backward, fused logits), pdf_layernorm_*, pdf_region_* / *_dev (sync-free pseudo-label pass) added. */
-#define PDF_ABI_VERSION 6
+ * 5 = round 5: pdf_wa_* (atomic-free window-attention backward, fused logits), pdf_layernorm_*, pdf_region_* / *_dev (sync-free pseudo-label pass) added;
+ * 7 = pdf_adam_step / pdf_adam_grad_unscale added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 7
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -418,6 +419,19 @@ int pdf_sgd_step(int nchunks, const void *tab, const int *chunks, float lr, floa
 int pdf_grad_unscale(int nchunks, const void *tab, const int *chunks, const float *inv_scale, float *found_inf, void *stream);
 int pdf_scaler_update(float *scale, float *inv_scale, int *growth_tracker, float *found_inf, float growth_factor, float backoff_factor,
                       int growth_interval, void *stream);
+/* Adam / AdamW (torch.optim.Adam / torch.optim.AdamW, the single-tensor non-capturable arithmetic of torch/optim/adam.py; no amsgrad, no
+ * maximize -- the optimizer of configs/scannet/openseg-pt-v1-0-*.py and of the openseg-st-v1m1 configs) over every tensor of one parameter
+ * group.  tab: ntensors records {float *param; const float *grad; float *exp_avg; float *exp_avg_sq; float *step; long length; long pad[2]}
+ * (64 bytes) in device memory; chunks as for pdf_sgd_step (pdf_sgd_chunk() values per chunk).  step points at that tensor's own float32 step
+ * count on the device: a one-thread-per-tensor launch adds 1 to each, then the update launch reads it for the bias corrections
+ * 1 - beta^step, formed in double from THIS call's betas (OneCycleLR moves beta1 between calls).  decoupled: 1 = AdamW (p *= 1 - lr wd),
+ * 0 = Adam's L2 form (g += wd p).  param / exp_avg / exp_avg_sq / step are updated in place.
+ * found_inf (device float, may be NULL): non-zero = parameters, both moments and every step count stay untouched.
+ * PDF_ERR_BAD_ARG before any launch: null tables, nchunks < 0, ntensors <= 0 with chunks to run, lr < 0, eps < 0, weight_decay < 0, a
+ * beta outside [0, 1) (NaN included).  pdf_adam_grad_unscale is pdf_grad_unscale over this 64-byte record. */
+int pdf_adam_step(int nchunks, int ntensors, const void *tab, const int *chunks, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int decoupled, const float *found_inf, void *stream);
+int pdf_adam_grad_unscale(int nchunks, const void *tab, const int *chunks, const float *inv_scale, float *found_inf, void *stream);
 
 /* ---- libs/pointops2 window attention: the CSR-by-query v2 / v3 launchers of
  * libs/pointops2/src/attention_v2/attention_cuda_kernel_v2.h and libs/pointops2/src/rpe_v2/relative_pos_encoding_cuda_kernel_v2.h,

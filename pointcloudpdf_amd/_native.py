@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 6   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 7   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -698,6 +698,11 @@ class HipBackend(CBackend):
         lib.pdf_grad_unscale.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_scaler_update.restype = c_int
         lib.pdf_scaler_update.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
+        lib.pdf_adam_step.restype = c_int
+        lib.pdf_adam_step.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, c_int, c_void_p, c_void_p]
+        lib.pdf_adam_grad_unscale.restype = c_int
+        lib.pdf_adam_grad_unscale.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_linbn_forward.restype = c_int
         lib.pdf_linbn_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
         lib.pdf_linbn_backward.restype = c_int

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from . import point_transformer, recognizer, segmentor  # noqa: F401  (registers the classes)
 from .model_hook import BaseModelHook
+from .optim import OPTIMIZERS, FusedAdam, FusedAdamW, FusedOptimizer, build_optimizer, build_scheduler  # noqa: F401  (re-exported)
 from .registry import MODELS, RECOGNIZER
 
 PT_V1_HOOKS = {  # configs/s3dis/openseg-pt-v1-0-pointpdf-v1m1-base.py:11-27
@@ -882,7 +883,7 @@ class FlatGradAllReduce:
         torch._foreach_copy_([g for _, g in have], [v for v, _ in have])
 
 
-class FusedSGD(torch.optim.Optimizer):
+class FusedSGD(FusedOptimizer):
     """``torch.optim.SGD(params, lr, momentum, weight_decay)`` (dampening 0, no Nesterov: what the reference's configs build,
     pointcept/utils/optimizer.py) as ONE HIP launch per parameter group and step over all of the group's tensors (csrc/optim.hip).
     torch's fused multi-tensor SGD needs 13 launches / 275 us for this model's 304 tensors; this is one launch / ~30 us.  Same
@@ -897,103 +898,21 @@ class FusedSGD(torch.optim.Optimizer):
     ``nesterov`` and ``maximize`` are refused at ``step()``.  Parameter and momentum pointers are read at every step (``model.to()``,
     ``load_state_dict`` may move them)."""
 
-    RING = 8   # pinned pointer tables in flight (the host may run several steps ahead of the device)
     SGD_DEFAULTS = dict(dampening=0, nesterov=False, maximize=False, foreach=None, differentiable=False, fused=None)   # torch.optim.SGD's other keys
 
-    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, backend=None):
-        import ctypes
-        from . import _native
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, backend=None, **options):
+        unknown = set(options) - set(self.SGD_DEFAULTS)
+        if unknown:
+            raise TypeError(f"FusedSGD: unexpected arguments {sorted(unknown)}")
+        super().__init__(params, dict(lr=float(lr), momentum=float(momentum), weight_decay=float(weight_decay), **{**self.SGD_DEFAULTS, **options}),
+                         backend=backend)
 
-        self.be = backend if backend is not None else _native.hip_backend()   # (backend: tests of the host logic without a GPU)
-        self.ctypes = ctypes
-        self._rows = 0
-        self._ring, self._tabs, self._spare, self._captured, self._plans, self._n = [], [], [], [], {}, 0
-        super().__init__(params, dict(lr=float(lr), momentum=float(momentum), weight_decay=float(weight_decay), **self.SGD_DEFAULTS))
-        every = [p for group in self.param_groups for p in group["params"]]
-        assert every and all(p.dtype == torch.float32 and p.is_contiguous() for p in every)
-        self.device = every[0].device
-        for p in every:
-            self.state[p]["momentum_buffer"] = torch.zeros_like(p)
-        self._table_cache, self._table_cache_on = {}, os.environ.get("PDFOPS_SGD_TABLE_CACHE") != "0"
-        self.chunk = int(self.be.lib.pdf_sgd_chunk()) if self.be is not None else 4096
-        self._size_tables()
-        self.reserve_capture_tables(2 * len(self.param_groups))
+    def _init_state(self, p):
+        self.state[p]["momentum_buffer"] = torch.zeros_like(p)
 
-    def add_param_group(self, param_group):
-        """torch.optim.Optimizer.add_param_group + the pointer tables re-sized for the largest group (they are pinned once, not per step)."""
-        super().add_param_group(param_group)
-        group = self.param_groups[-1]
-        group["params"] = [p for p in group["params"] if p.requires_grad]
-        if self._rows:   # (during __init__ the tables are sized once, after every group is in)
-            self._size_tables()
-
-    def _size_tables(self):
-        rows = max(len(g["params"]) for g in self.param_groups)
-        if rows <= self._rows:
-            return
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FusedSGD.add_param_group: pinning host memory is not allowed during stream capture")
-        for _, ev in self._ring:   # tables of steps still in flight stay alive until their launch has run
-            if ev is not None:
-                ev.synchronize()
-        self._rows = rows
-        pin = (lambda t: t.pin_memory()) if self.device.type == "cuda" else (lambda t: t)
-        self._ring = [(pin(torch.empty((rows, 4), dtype=torch.int64)), torch.cuda.Event() if self.device.type == "cuda" else None)
-                      for _ in range(self.RING)]
-        self._tabs = [torch.empty((rows, 4), dtype=torch.int64, device=self.device) for _ in range(self.RING)]
-        self._spare = [pin(torch.empty((rows, 4), dtype=torch.int64)) for _ in self._spare]
-        self._plans = {}
-
-    def reserve_capture_tables(self, n):
-        """Pinned pointer tables for ``n`` more (group, captured step) pairs; must be called outside stream capture."""
-        pin = (lambda t: t.pin_memory()) if self.device.type == "cuda" else (lambda t: t)
-        self._spare += [pin(torch.empty((self._rows, 4), dtype=torch.int64)) for _ in range(n)]
-
-    @property
-    def params(self):
-        return [p for group in self.param_groups for p in group["params"]]
-
-    def _plan(self, gi, have, params):
-        key = (gi, have)
-        if key not in self._plans:
-            import numpy as np
-
-            pairs = [(row, c) for row, i in enumerate(have) for c in range((params[i].numel() + self.chunk - 1) // self.chunk)]
-            lengths = np.array([params[i].numel() for i in have], dtype=np.int64)
-            self._plans[key] = (torch.tensor(pairs, dtype=torch.int32, device=self.device).contiguous(), len(pairs), lengths)
-        return self._plans[key]
-
-    def _tables(self, gi, group):
-        """Device table {param, grad, momentum, length} + chunk list of group ``gi`` for the parameters that have a gradient now.
-        -> (nchunks, tab, chunks, event | None) or None when no parameter of the group has a gradient."""
-        from . import _native
-
+    def _state_columns(self, rows, ps):
+        """Column 2 of the table {param, grad, momentum, length}."""
         f32 = torch.float32
-        params = group["params"]
-        all_grads = [p.grad for p in params]   # (one attribute read per parameter and step: 304 of them)
-        have = tuple(i for i, g in enumerate(all_grads) if g is not None)
-        if not have:
-            return None
-        _native.require_current_device(self._tabs[0])   # (launches go onto the current device's current stream)
-        chunks, nchunks, lengths = self._plan(gi, have, params)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if capturing:   # a captured step replays this copy + launch: the tables must outlive the graph and never be rewritten
-            if not self._spare:
-                raise RuntimeError("FusedSGD: more captured steps than pinned pointer tables (pinning host memory is not allowed "
-                                   "during stream capture); call reserve_capture_tables(n) before capturing")
-            host = self._spare.pop()
-            tab, ev = torch.empty((len(have), 4), dtype=torch.int64, device=self.device), None
-            self._captured.append((host, tab))
-        else:
-            slot = self._n % self.RING
-            host, ev = self._ring[slot]
-            tab = self._tabs[slot]
-            self._n += 1
-            ev.synchronize()   # (the copy AND the launch that last used this slot have run)
-        full = len(have) == len(all_grads)
-        grads = all_grads if full else [all_grads[i] for i in have]
-        fixed = [g if (g.dtype is f32 and g.is_contiguous()) else g.float().contiguous() for g in grads]   # (alive until queued)
-        ps = params if full else [params[i] for i in have]
         state = self.state
         bufs = []
         for q in ps:
@@ -1002,28 +921,7 @@ class FusedSGD(torch.optim.Optimizer):
             if buf is None or buf.shape != q.shape or buf.device != q.device or buf.dtype is not f32 or not buf.is_contiguous():
                 buf = st["momentum_buffer"] = torch.zeros_like(q) if buf is None else buf.to(q.device, f32).reshape(q.shape).contiguous()
             bufs.append(buf)
-        rows = host.numpy()[:len(have)]
-        rows[:, 0] = [q.data_ptr() for q in ps]
-        rows[:, 1] = [g.data_ptr() for g in fixed]
         rows[:, 2] = [b.data_ptr() for b in bufs]
-        rows[:, 3] = lengths
-        if not capturing and self._table_cache_on:
-            # Replayed steps hand the SAME gradient tensors back every time: the table of the last step is then still right, and the host
-            # -> device copy (19 KB through the copy engine, a cross-queue dependency in front of the optimizer launch: ~0.1 ms of idle
-            # time on a quiet device, ~0.45 ms beside the pre-pass queues, profiles/r06_z_timeline.txt) is skipped.  The cached table is
-            # its own device tensor, written only here.
-            last = self._table_cache.get(gi)
-            if last is not None and last[0].shape == rows.shape and (last[0] == rows).all():
-                return nchunks, last[1], chunks, ev, fixed
-            keep = torch.empty((len(have), 4), dtype=torch.int64, device=self.device)
-            keep.copy_(host[:len(have)], non_blocking=True)
-            self._table_cache[gi] = (rows.copy(), keep)
-            return nchunks, keep, chunks, ev, fixed
-        tab[:len(have)].copy_(host[:len(have)], non_blocking=True)
-        return nchunks, tab, chunks, ev, fixed
-
-    def _grad_key(self):
-        return tuple(p.grad.data_ptr() if p.grad is not None else 0 for group in self.param_groups for p in group["params"])
 
     @torch.no_grad()
     def step(self, closure=None, found_inf=None):
@@ -1034,11 +932,7 @@ class FusedSGD(torch.optim.Optimizer):
                 loss = closure()
         from . import _native
 
-        prepared, self._prepared = getattr(self, "_prepared", None), None
-        if prepared is not None:   # tables of an unscale_: valid only for the gradients they were built from (an iteration that aborted
-            key, prepared = prepared   # between unscale_ and step, or re-assigned gradients, must not reuse stale pointer tables)
-            if key != self._grad_key():
-                prepared = None
+        prepared = self._take_prepared()
         for gi, group in enumerate(self.param_groups):
             if group.get("dampening", 0) != 0 or group.get("nesterov", False) or group.get("maximize", False):
                 raise RuntimeError("FusedSGD: dampening / nesterov / maximize are not implemented (the reference's configs use none of them)")
@@ -1054,6 +948,9 @@ class FusedSGD(torch.optim.Optimizer):
             if rc != 0:
                 raise RuntimeError(f"pdf_sgd_step failed with status {rc}")
         return loss
+
+
+OPTIMIZERS.register_module(name="SGD", module=FusedSGD)
 
 
 class DeviceGradScaler:
@@ -1096,10 +993,10 @@ class DeviceGradScaler:
 
     @torch.no_grad()
     def unscale_(self, optimizer):
-        """g *= 1 / scale for every gradient of ``optimizer`` (a FusedSGD) in one launch per group; sets found_inf."""
+        """g *= 1 / scale for every gradient of ``optimizer`` (a FusedSGD / FusedAdam / FusedAdamW) in one launch per group; sets found_inf."""
         if not self.enabled or self._unscaled:
             return
-        if not isinstance(optimizer, FusedSGD):
+        if not isinstance(optimizer, FusedOptimizer):
             raise TypeError("DeviceGradScaler drives engine.FusedSGD (the guarded update is part of its kernel); use torch.amp.GradScaler "
                             "with other optimizers")
         from . import _native
@@ -1112,10 +1009,11 @@ class DeviceGradScaler:
             if t is None:
                 continue
             nchunks, tab, chunks, _ev, _alive = t
-            rc = optimizer.be.lib.pdf_grad_unscale(nchunks, tab.data_ptr(), chunks.data_ptr(), self._f[1:2].data_ptr(), self._f[2:3].data_ptr(),
-                                                   ctypes.c_void_p(_native.raw_stream()))
+            unscale = getattr(optimizer.be.lib, optimizer.UNSCALE)   # (the entry that reads this optimizer's record layout)
+            rc = unscale(nchunks, tab.data_ptr(), chunks.data_ptr(), self._f[1:2].data_ptr(), self._f[2:3].data_ptr(),
+                         ctypes.c_void_p(_native.raw_stream()))
             if rc != 0:
-                raise RuntimeError(f"pdf_grad_unscale failed with status {rc}")
+                raise RuntimeError(f"{optimizer.UNSCALE} failed with status {rc}")
         optimizer._prepared = (optimizer._grad_key(), prepared)   # the step of this iteration reuses the tables (same gradients, same pointers)
         self._unscaled, self._prepared_for = True, optimizer
 
