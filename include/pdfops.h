@@ -40,8 +40,9 @@ extern "C" {
  * without a bump, see ADVICE of round 3); 4 = round 4: `mma_input` per call on the pdf_rowlin_ / pdf_block_ / pdf_bottleneck_ / pdf_linbn_ /
  * pdf_td_ entries, pdf_set_mma_input / pdf_get_mma_input / pdf_tickets_* removed, pdf_sgd_step takes a found-inf flag;
  * 5 = round 5: pdf_wa_* (atomic-free window-attention backward, fused logits), pdf_layernorm_*, pdf_region_* / *_dev (sync-free pseudo-label pass) added;
- * 7 = pdf_adam_step / pdf_adam_grad_unscale added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 7
+ * 7 = pdf_adam_step / pdf_adam_grad_unscale added (no existing parameter list changed);
+ * 8 = pdf_fragment_bounds / pdf_fragment_gather / pdf_fragment_vote added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 8
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -515,6 +516,31 @@ int pdf_aug_elastic_apply(int b, long n, const long long *offset, const long lon
  * (one point per voxel of a GridSample test fragment); score may be NULL. */
 int pdf_vote_accumulate(long n, int c, const float *logits, const float *score, const long *index, float *pred,
                         float *score_sum, float *score_cnt, void *stream);
+
+/* ---- batched test-time fragments of ONE augmented scene (csrc/fragments.hip; pointcept/datasets/transform.py:858-887,
+ * datasets/defaults.py:96-129, engines/test.py:206-251).  The fragment table (voxelize.fragment_table): order (n) int64 = point ids,
+ * key-sorted, original order inside a voxel; vstart (v) / count (v) int64 = every voxel's run in `order`; voxel_of (n) int64 = the voxel
+ * of every sorted position.  Fragment f holds order[vstart[i] + f % count[i]] of every voxel i; a call covers fragments f0 .. f0 + g - 1,
+ * row r = (f - f0) v + i.  Every entry validates before any launch -- PDF_ERR_BAD_ARG: a null table / output, n < 0, v < 0, v > n,
+ * f0 < 0, g < 1 (gather: g > 256, or g v >= 2^31 -- out_offset is int32), f64 not 0 / 1 -- and is a no-op for v == 0.
+ * pdf_fragment_bounds: bounds (g, 6) float64 = [min xyz | max xyz] of the selected coordinates (coord (n, 3) fp32, or fp64 with f64 = 1;
+ *   exact either way); ws: pdf_fragment_bounds_ws_doubles(g) doubles.
+ * pdf_fragment_gather: index (g v) int64; out_coord (g v, 3) fp32 = coord[p] - shift[f - f0], shift (g, 3) in coord's dtype, subtracted in
+ *   that dtype and rounded once to fp32; out_feat (g v, c) fp32 = nseg (1..4) segments side by side: seg_src[k] == NULL -> the shifted
+ *   coordinate (seg_w[k] must be 3), else the (n, seg_w[k] in 1..4) fp32 array seg_src[k] gathered; seg_src / seg_w are HOST arrays of
+ *   nseg entries; out_grid (g v, 3) int64 = grid_src[p] (both NULL, or both given); out_offset (g) int32 = (k + 1) v.
+ * pdf_fragment_vote: logits (g v, c), score (g v) or NULL, in gather order, folded into pred (n, c) / score_sum (n) / score_cnt (n)
+ *   without atomics, a point's fragments in ascending order: bit-identical to g successive pdf_vote_accumulate calls. */
+long pdf_fragment_bounds_ws_doubles(int g);
+int pdf_fragment_bounds(long n, long v, int f0, int g, int f64, const void *coord, const long *order, const long *vstart,
+                        const long *count, double *ws, double *bounds, void *stream);
+int pdf_fragment_gather(long n, long v, int f0, int g, int f64, const void *coord, const long *order, const long *vstart,
+                        const long *count, const void *shift, int nseg, const float *const *seg_src, const int *seg_w,
+                        const long long *grid_src, long *index, float *out_coord, float *out_feat, long long *out_grid,
+                        int *out_offset, void *stream);
+int pdf_fragment_vote(long n, long v, int f0, int g, int c, const float *logits, const float *score, const long *order,
+                      const long *vstart, const long *count, const long *voxel_of, float *pred, float *score_sum,
+                      float *score_cnt, void *stream);
 
 /* Fixed-radius neighbour table of a batch with itself over the kNN grid (cells >= radius): idx (n, nsample) = the first nsample
  * points of the query's scene in index order within `radius`, -1 / 1e10 padded -- the results of pdf_random_ball_query with the

@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 7   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 8   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -74,6 +74,9 @@ _HIP_ONLY_PROTOS = {
     "aug_elastic_apply": "ilpppppdpp",
     "radius_neighbors_self": "iifppipppl",
     "vote_accumulate": "lipppppp",
+    "fragment_bounds": "lliiipppppp",
+    "fragment_gather": "lliiipppppipppppppp",
+    "fragment_vote": "lliiippppppppp",
     "graph_forest": "lipppppipppl",
     "gmm2_1d": "ipppidd",
     "dot_prod_with_idx_forward_v3_l": "iiiiipppppppp",
@@ -637,6 +640,8 @@ class HipBackend(CBackend):
         self.last_fps_stats = None
         lib.pdf_aug_bounds_workspace_doubles.restype = c_int
         lib.pdf_aug_bounds_workspace_doubles.argtypes = [c_int]
+        lib.pdf_fragment_bounds_ws_doubles.restype = c_long
+        lib.pdf_fragment_bounds_ws_doubles.argtypes = [c_int]
         lib.pdf_abi_version.restype = c_int
         lib.pdf_build_info.restype = ctypes.c_char_p
         got = int(lib.pdf_abi_version())
@@ -1740,6 +1745,98 @@ class HipBackend(CBackend):
         nul = ctypes.c_void_p(None)
         self._call("vote_accumulate", n, c, logits, nul if score is None else score, index, pred,
                    nul if score is None else score_sum, nul if score is None else score_cnt)
+
+    # -- batched test-time fragments (csrc/fragments.hip; pointcloudpdf_amd/testing.py drives them) ------------------------------------
+    @staticmethod
+    def _fragment_table(table, f0, g, coord=None):
+        """-> (n, v) of a ``voxelize.fragment_table`` result after its dtype / shape checks."""
+        order, vstart, count = table["order"], table["vstart"], table["count"]
+        _check(order, torch.int64, "order"); _check(vstart, torch.int64, "vstart"); _check(count, torch.int64, "count")
+        n, v = order.shape[0], count.shape[0]
+        if order.dim() != 1 or count.dim() != 1 or vstart.shape != (v,) or v > n:
+            raise ValueError("fragment table: order (n), vstart (v), count (v) with v <= n")
+        if int(f0) < 0 or int(g) < 1:
+            raise ValueError(f"fragment batch: f0 >= 0 and g >= 1 (got f0={f0}, g={g})")
+        if coord is not None:
+            if coord.dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"coord: expected float32 or float64, got {coord.dtype}")
+            _check(coord, coord.dtype, "coord")
+            if coord.shape != (n, 3):
+                raise ValueError(f"coord: expected ({n}, 3), got {tuple(coord.shape)}")
+        return n, v
+
+    def fragment_bounds(self, coord, table, f0, g):
+        """-> (g, 6) float64 [min xyz | max xyz] of the coordinates test fragments f0 .. f0 + g - 1 select (exact)."""
+        n, v = self._fragment_table(table, f0, g, coord)
+        ws = self._new(coord, (max(int(self.lib.pdf_fragment_bounds_ws_doubles(int(g))), 1),), torch.float64)
+        bounds = self._new(coord, (int(g), 6), torch.float64)
+        self._call("fragment_bounds", n, v, int(f0), int(g), 1 if coord.dtype == torch.float64 else 0, coord, table["order"],
+                   table["vstart"], table["count"], ws, bounds)
+        return bounds
+
+    def fragment_gather(self, coord, table, f0, g, shift, feat_segments, grid_coord=None):
+        """The collated batch of test fragments f0 .. f0 + g - 1 in one launch.  shift (g, 3) in coord's dtype; ``feat_segments``: the
+        Collect.feat_keys entries in order, each ``None`` (the shifted coordinate) or an (n, w <= 4) float32 tensor; grid_coord (n, 3)
+        int64 or None.  -> dict(index (g v) int64, coord (g v, 3) f32, feat (g v, c) f32, offset (g) int32[, grid_coord (g v, 3) int64])."""
+        n, v = self._fragment_table(table, f0, g, coord)
+        g = int(g)
+        _check(shift, coord.dtype, "shift")
+        if shift.shape != (g, 3):
+            raise ValueError(f"shift: expected ({g}, 3), got {tuple(shift.shape)}")
+        if not 1 <= len(feat_segments) <= 4 or g > 256:
+            raise ValueError("fragment_gather: 1..4 feat segments, at most 256 fragments per batch")
+        widths = []
+        for k, t in enumerate(feat_segments):
+            if t is None:
+                widths.append(3)
+                continue
+            _check(t, torch.float32, f"feat segment {k}")
+            if t.dim() != 2 or t.shape[0] != n or not 1 <= t.shape[1] <= 4:
+                raise ValueError(f"feat segment {k}: expected ({n}, w <= 4), got {tuple(t.shape)}")
+            self._ptr(t)
+            if t.device != coord.device:
+                raise PdfOpsError(f"feat segment {k} on {t.device}, coord on {coord.device}")
+            widths.append(int(t.shape[1]))
+        if grid_coord is not None:
+            _check(grid_coord, torch.int64, "grid_coord")
+            if grid_coord.shape != (n, 3):
+                raise ValueError(f"grid_coord: expected ({n}, 3)")
+        rows, c = g * v, sum(widths)
+        if rows > 2 ** 31 - 1:
+            raise ValueError(f"fragment_gather: {g} fragments of {v} voxels do not fit the int32 offset")
+        out = dict(index=self._new(coord, (rows,), torch.int64), coord=self._new(coord, (rows, 3), torch.float32),
+                   feat=self._new(coord, (rows, c), torch.float32), offset=self._new(coord, (g,), torch.int32))
+        if v == 0:
+            out["offset"].zero_()
+        if grid_coord is not None:
+            out["grid_coord"] = self._new(coord, (rows, 3), torch.int64)
+        nul = ctypes.c_void_p(None)
+        seg_src = (c_void_p * 4)(*[None if t is None else t.data_ptr() for t in feat_segments])
+        seg_w = (c_int * 4)(*widths)
+        self._call("fragment_gather", n, v, int(f0), g, 1 if coord.dtype == torch.float64 else 0, coord, table["order"], table["vstart"],
+                   table["count"], shift, len(feat_segments), seg_src, seg_w, nul if grid_coord is None else grid_coord, out["index"],
+                   out["coord"], out["feat"], out.get("grid_coord", nul), out["offset"])
+        return out
+
+    def fragment_vote(self, logits, score, table, f0, g, pred, score_sum, score_cnt):
+        """Fold the batch of fragments f0 .. f0 + g - 1 (logits (g v, c), score (g v) or None, rows in gather order) into the running vote
+        -- no atomics, a point's fragments in ascending order: bit-identical to g successive ``vote_accumulate`` calls."""
+        n, v = self._fragment_table(table, f0, g)
+        g = int(g)
+        _check(table["voxel_of"], torch.int64, "voxel_of")
+        _check(logits, torch.float32, "logits"); _check(pred, torch.float32, "pred")
+        if table["voxel_of"].shape != (n,):
+            raise ValueError(f"voxel_of: expected ({n},)")
+        if logits.dim() != 2 or logits.shape[0] != g * v or pred.dim() != 2 or pred.shape != (n, logits.shape[1]):
+            raise ValueError(f"fragment_vote: logits ({g * v}, c) and pred ({n}, c) expected, got {tuple(logits.shape)}, {tuple(pred.shape)}")
+        if score is not None:
+            _check(score, torch.float32, "score"); _check(score_sum, torch.float32, "score_sum"); _check(score_cnt, torch.float32, "score_cnt")
+            if score.shape != (g * v,) or score_sum.shape != (n,) or score_cnt.shape != (n,):
+                raise ValueError("fragment_vote: score (g v), score_sum (n), score_cnt (n)")
+        nul = ctypes.c_void_p(None)
+        self._call("fragment_vote", n, v, int(f0), g, logits.shape[1], logits, nul if score is None else score, table["order"],
+                   table["vstart"], table["count"], table["voxel_of"], pred, nul if score is None else score_sum,
+                   nul if score is None else score_cnt)
 
     def group_forward(self, feat, xyz, new_xyz, idx, with_xyz):
         _check(feat, torch.float32, "feat"); _check(idx, torch.int32, "idx")

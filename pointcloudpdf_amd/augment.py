@@ -353,6 +353,28 @@ class RemapLabel:
 
 
 @TRANSFORMS.register_module()
+class Copy:
+    """transform.py:53-68.  A scene-level op of the TEST pipeline (testing.TestPipeline applies it); ``Compose`` refuses it."""
+    test_only = True
+
+    def __init__(self, keys_dict=None):
+        self.keys_dict = dict(coord="origin_coord", segment="origin_segment") if keys_dict is None else dict(keys_dict)
+
+
+@TRANSFORMS.register_module()
+class RandomRotateTargetAngle:
+    """transform.py:264-300.  Test-time augmentation op (testing.TestPipeline applies it when it is deterministic); ``Compose`` refuses it."""
+    test_only = True
+
+    def __init__(self, angle=(1 / 2, 1, 3 / 2), center=None, axis="z", always_apply=False, p=0.75):
+        self.angle = [angle] if not hasattr(angle, "__len__") else list(angle)
+        self.center, self.axis = center, axis
+        self.p = p if not always_apply else 1
+        if axis not in ("x", "y", "z"):
+            raise NotImplementedError(f"RandomRotateTargetAngle: axis {axis!r}")
+
+
+@TRANSFORMS.register_module()
 class ToTensor:
     pass
 
@@ -378,7 +400,7 @@ class Compose:
         for i, cfg in enumerate(cfg_list):
             cfg = dict(cfg)
             name = cfg.get("type")
-            if name not in TRANSFORMS:
+            if name not in TRANSFORMS or getattr(TRANSFORMS.get(name), "test_only", False):
                 raise KeyError(f"augment.Compose: transform type {name!r} is not supported on the device")
             t = TRANSFORMS.build(cfg)
             t.stream = 16 * (i + 1)

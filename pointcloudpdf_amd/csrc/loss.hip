@@ -5,6 +5,7 @@
 // slot and a one-workgroup sum over the slots (sum of losses, number of counted rows; fixed order, no atomics).  The forward also leaves softmax - onehot (zero on ignored rows) in
 // `grad`, so the backward is one scaled copy.  Bound: HBM (8NC bytes forward).
 #include "pdfops_common.h"
+#include "vote_row.h"
 
 namespace {
 
@@ -74,15 +75,8 @@ __global__ __launch_bounds__(LB) void k_vote(long n, int c, const float *__restr
                                              const long *__restrict__ index, float *__restrict__ pred, float *__restrict__ score_sum,
                                              float *__restrict__ score_cnt) {
     for (long r = (long)blockIdx.x * LB + threadIdx.x; r < n; r += (long)gridDim.x * LB) {
-        const float *x = logits + r * c;
-        float m = x[0];
-        for (int j = 1; j < c; ++j) m = fmaxf(m, x[j]);
-        float s = 0.f;
-        for (int j = 0; j < c; ++j) s += __expf(x[j] - m);
-        const float inv = 1.f / s;
         const long dst = index[r];
-        float *p = pred + dst * c;
-        for (int j = 0; j < c; ++j) p[j] += __expf(x[j] - m) * inv;
+        pdf_vote_row(logits + r * c, c, pred + dst * c);   // (vote_row.h: shared with the batched voter of fragments.hip)
         if (score) { score_sum[dst] += score[r]; score_cnt[dst] += 1.f; }
     }
 }

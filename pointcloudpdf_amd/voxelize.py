@@ -68,3 +68,45 @@ def grid_sample(coord, offset, grid_size, mode="train", generator=None, float32_
         cmax = int(count.max().item()) if nv else 0
         out["fragments"] = [order[vstart + (i % count)] for i in range(cmax)]
     return out
+
+
+def fragment_table(coord, offset, grid_size, float32_division=False, offset_host=None, hash_fn=None):
+    """The table ``grid_sample(mode="test")`` computes before its Python loop, without the loop: fragment f of a scene holds
+    ``order[vstart[v] + f % count[v]]`` of every voxel v of that scene (transform.py:861-863).  -> dict with
+         order (N) point ids scene-major / key-sorted / original order inside a voxel, vstart (V) first position of every voxel in
+         ``order``, count (V) points per voxel, voxel_of (N) the voxel of every sorted position, inverse (N) the voxel of every point
+         (global numbering; with one scene = ``np.unique(..., return_inverse)`` scattered back, transform.py:866-867),
+         grid_coord (N,3) int64, key (N), voxel_offset (B) cumulative voxel counts, cmax (host int) = count.max() = number of fragments.
+    ``hash_fn(coord, offset, gs, min_grid) -> (grid, key)`` replaces the HIP key pass (testing.py passes its torch composition for
+    host tensors).  The consumers are ``pdf_fragment_bounds / _gather / _vote`` (csrc/fragments.hip)."""
+    n, b = coord.shape[0], offset.shape[0]
+    ends = offset_host if offset_host is not None else [int(v) for v in offset.tolist()]
+    gs = [float(grid_size)] * 3 if not hasattr(grid_size, "__len__") else [float(g) for g in grid_size]
+    starts = [0] + ends[:-1]
+    mins = torch.stack([coord[s:e].amin(0) if e > s else coord.new_zeros(3) for s, e in zip(starts, ends)])   # (B,3)
+    g = torch.tensor(gs, dtype=torch.float32 if float32_division else torch.float64, device=coord.device)
+    min_grid = torch.floor(mins.to(g.dtype) / g).long().contiguous()
+    if hash_fn is not None:
+        grid, key = hash_fn(coord, offset, gs, min_grid)
+    elif coord.dtype == torch.float64:
+        if float32_division:
+            raise ValueError("fragment_table: float32_division applies to float32 coordinates only")
+        grid, key = _native.backend_for(coord).grid_hash_f64(coord.contiguous(), offset.int().contiguous(), gs, min_grid)
+    else:
+        grid, key = _native.backend_for(coord).grid_hash(coord.contiguous(), offset.int().contiguous(), gs, min_grid, float32_division)
+    scene = torch.bucketize(torch.arange(n, device=coord.device), offset.long(), right=True)
+    o1 = torch.sort(key ^ _SIGN, stable=True)[1]         # unsigned order under a signed sort
+    order = o1[torch.sort(scene[o1], stable=True)[1]] if b > 1 else o1
+    ks, ss = key[order], scene[order]
+    new_voxel = torch.ones(n, dtype=torch.bool, device=coord.device)
+    if n > 1:
+        new_voxel[1:] = (ks[1:] != ks[:-1]) | (ss[1:] != ss[:-1])
+    voxel_of = torch.cumsum(new_voxel, 0) - 1
+    nv = int(voxel_of[-1].item()) + 1 if n else 0
+    count = torch.bincount(voxel_of, minlength=nv)
+    vstart = torch.cumsum(count, 0) - count
+    inverse = torch.empty(n, dtype=torch.long, device=coord.device)
+    inverse[order] = voxel_of
+    voxel_offset = torch.cumsum(torch.bincount(ss[vstart], minlength=b), 0)
+    return dict(order=order.contiguous(), vstart=vstart.contiguous(), count=count.contiguous(), voxel_of=voxel_of.contiguous(),
+                inverse=inverse, grid_coord=grid, key=key, voxel_offset=voxel_offset.int(), cmax=int(count.max().item()) if nv else 0)
