@@ -41,8 +41,9 @@ extern "C" {
  * pdf_td_ entries, pdf_set_mma_input / pdf_get_mma_input / pdf_tickets_* removed, pdf_sgd_step takes a found-inf flag;
  * 5 = round 5: pdf_wa_* (atomic-free window-attention backward, fused logits), pdf_layernorm_*, pdf_region_* / *_dev (sync-free pseudo-label pass) added;
  * 7 = pdf_adam_step / pdf_adam_grad_unscale added (no existing parameter list changed);
- * 8 = pdf_fragment_bounds / pdf_fragment_gather / pdf_fragment_vote added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 8
+ * 8 = pdf_fragment_bounds / pdf_fragment_gather / pdf_fragment_vote added (no existing parameter list changed);
+ * 9 = pdf_radius_neighbors_self_adaptive added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 9
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -548,6 +549,17 @@ int pdf_fragment_vote(long n, long v, int f0, int g, int c, const float *logits,
  * pseudo-label pass, pointpdf_v1m1_base.py:122-130).  Workspace: pdf_knn_workspace_bytes(b, n, 0); b <= 64. */
 int pdf_radius_neighbors_self(int n, int nsample, float radius, const float *xyz, const int *offset, int b, int *idx, float *dist2,
                               void *workspace, long workspace_bytes, void *stream);
+/* The same table with one radius PER SCENE, derived on the device (the reference's adaptive_radius=True, pointpdf_v1m1_base.py:137-149):
+ * r_s = min over the three axes of ((max_a - min_a) + pad) / divisor, fp32 in exactly that order -- with divisor = 16, pad = 1e-6 the value
+ * of ((c.max(0)[0] - c.min(0)[0] + 1e-6) / 16).min() on the scene's float32 coordinates.  The extents are the ones the grid setup reduces
+ * anyway; r_s is written to radii[s] (b floats, out), sizes the scene's cells (cell >= r_s * 1.0001) and is the radius of every query of
+ * scene s: accepted are d2 < r_s * r_s or d2 <= 1e-5, as above.  A one-point scene, coincident points or a flat axis give
+ * r_s = pad / divisor: every point then still finds itself and everything within sqrt(1e-5) = 3.16 mm -- both entries size their cells by
+ * max(radius, 3.1623 mm), so the 27 cells around a query cover that reach whatever the radius.  A scene without points gets r_s = pad / divisor.  No host read, no allocation: the call
+ * can be recorded into a graph.  Same workspace, same b <= 64, same argument errors as the fixed entry, plus divisor <= 0, pad < 0 or a
+ * null radii; n == 0 launches nothing and leaves radii untouched. */
+int pdf_radius_neighbors_self_adaptive(int n, int nsample, float divisor, float pad, const float *xyz, const int *offset, int b,
+                                       int *idx, float *dist2, float *radii, void *workspace, long workspace_bytes, void *stream);
 
 /* The graph stage of the PDF pseudo-label pass (pointpdf_v1m1_base.py:309-380: scipy.sparse.csgraph.minimum_spanning_tree over the
  * region's neighbour similarities, :340; connected_components of the weak tree edges, :360) for ONE scene, one workgroup.

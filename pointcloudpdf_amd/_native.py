@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 8   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 9   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -73,6 +73,7 @@ _HIP_ONLY_PROTOS = {
     "aug_elastic_blur": "ilpppi",
     "aug_elastic_apply": "ilpppppdpp",
     "radius_neighbors_self": "iifppipppl",
+    "radius_neighbors_self_adaptive": "iiffppippppl",
     "vote_accumulate": "lipppppp",
     "fragment_bounds": "lliiipppppp",
     "fragment_gather": "lliiipppppipppppppp",
@@ -1578,6 +1579,39 @@ class HipBackend(CBackend):
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=xyz.device)
         self._call("radius_neighbors_self", n, int(nsample), float(radius), xyz, offset, b, idx, dist2, ws, nbytes)
         return idx, dist2
+
+    ADAPTIVE_DIVISOR, ADAPTIVE_PAD = 16.0, 1e-6   # pointpdf_v1m1_base.py:137-140: ((max - min + 1e-6) / 16).min()
+
+    def radius_neighbors_self_adaptive(self, nsample, xyz, offset):
+        """-> idx (n, nsample) int32, dist2 (n, nsample), radii (b,) float32: ``radius_neighbors_self`` with the per-scene radius
+        min over the axes of ((max - min) + 1e-6) / 16, derived on the device (no host read: capturable)."""
+        _check(xyz, torch.float32, "xyz"); _check(offset, torch.int32, "offset")
+        n, b = xyz.shape[0], offset.shape[0]
+        if b > 64:   # the grid workspace is sized for <= 64 scenes: one fixed-radius query per scene, the radii read on the host
+            if torch.cuda.is_current_stream_capturing():
+                raise PdfOpsError("radius_neighbors_self_adaptive: more than 64 scenes need a host read of the radii, "
+                                  "which a stream capture cannot hold")
+            ends = offset.tolist()
+            starts = [0] + ends[:-1]
+            extent = lambda c: c.max(0)[0] - c.min(0)[0] if c.shape[0] else c.new_zeros(3)   # (a scene without points: extent 0, as the kernel)
+            radii = torch.stack([((extent(xyz[s:e]) + self.ADAPTIVE_PAD) / self.ADAPTIVE_DIVISOR).min() for s, e in zip(starts, ends)])
+            idx, dist2 = [], []
+            for s, e, r in zip(starts, ends, radii.tolist()):
+                if e == s:
+                    continue
+                i, d = self.radius_neighbors_self(nsample, r, xyz[s:e], torch.tensor([e - s], dtype=torch.int32, device=xyz.device))
+                idx.append(torch.where(i >= 0, i + s, i)); dist2.append(d)
+            if not idx:
+                return self._new(xyz, (0, nsample), torch.int32), self._new(xyz, (0, nsample), torch.float32), radii
+            return torch.cat(idx), torch.cat(dist2), radii
+        idx = self._new(xyz, (n, nsample), torch.int32)
+        dist2 = self._new(xyz, (n, nsample), torch.float32)
+        radii = self._new(xyz, (b,), torch.float32)
+        nbytes = int(self.lib.pdf_knn_workspace_bytes(b, n, 0))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=xyz.device)
+        self._call("radius_neighbors_self_adaptive", n, int(nsample), self.ADAPTIVE_DIVISOR, self.ADAPTIVE_PAD, xyz, offset, b, idx, dist2,
+                   radii, ws, nbytes)
+        return idx, dist2, radii
 
     def graph_forest(self, n, eu, ev, nodes, weight=None, active=None, want_chosen=True):
         """One scene's region graph (pseudo-label pass, pointpdf_v1m1_base.py:309-380): directed entries (eu[e], ev[e]) with ``weight[e]``

@@ -24,6 +24,10 @@ extern "C" int pdf_knn_query_list(int m, int nsample, const float *xyz, const fl
 namespace kg {
 
 constexpr int CAP_CELLS = 1 << 20;  // cells per scene
+// The radius queries accept d2 < r^2 OR d2 <= 1e-5: whatever the radius, a query reaches sqrt(1e-5) = 3.16228 mm.  Their 27 cells cover the
+// accepted set only if the cell is at least that wide, so the cell bound is max(radius, this) -- the same cell as before for every radius
+// from 3.1623 mm up; below it (the adaptive radius of a flat or thin scene: pad / divisor) the bound is what keeps the table exact.
+constexpr float RQ_MIN_REACH = 3.1623e-3f;
 constexpr int PB = 256;
 
 struct SceneGrid {      // 16 floats / ints per scene in the workspace
@@ -52,8 +56,14 @@ __host__ __device__ inline Layout make_layout(int b, int n, int m) {
     return L;
 }
 
+// `radii` (null for every caller with a scalar cell bound): the ADAPTIVE radius of the scene, pointpdf_v1m1_base.py:137-140 --
+// min over the axes of ((hi - lo) + pad) / divisor, fp32 in that order -- is derived from the extents reduced here, written to radii[s] and
+// takes the place of `min_cell` (cell >= max(radius, RQ_MIN_REACH) * 1.0001, what the fixed-radius entry passes as a scalar).  A scene
+// without points has extent 0.  The cell-growing loop below ends whatever the bound: every factor of the cell count is
+// <= longest / cell + 1 <= 1001 at entry, and the cell only grows -- a radius of pad / divisor (one point, coincident points, a flat axis)
+// never makes the cell SMALLER.
 __global__ __launch_bounds__(PB) void k_grid_setup(const float *__restrict__ xyz, const int *__restrict__ offset, SceneGrid *__restrict__ grids, float ppc,
-                                                   float min_cell) {
+                                                   float min_cell, float *__restrict__ radii, float divisor, float pad) {
     __shared__ float red[6][PB / 64];
     const int s = blockIdx.x;
     const int start = s == 0 ? 0 : offset[s - 1], end = offset[s];
@@ -87,6 +97,12 @@ __global__ __launch_bounds__(PB) void k_grid_setup(const float *__restrict__ xyz
         // target ~ppc points per cell if the points filled the box; never more than CAP_CELLS cells
         float cell = cbrtf(ext[0] * ext[1] * ext[2] * ppc / (float)(n > 0 ? n : 1));
         const float longest = fmaxf(ext[0], fmaxf(ext[1], ext[2]));
+        if (radii) {
+            float r = 3.0e38f;
+            for (int a = 0; a < 3; ++a) r = fminf(r, ((n > 0 ? h[a] - l[a] : 0.f) + pad) / divisor);
+            radii[s] = r;
+            min_cell = fmaxf(r, RQ_MIN_REACH) * 1.0001f;
+        }
         cell = fmaxf(fmaxf(cell, longest / 1000.f), min_cell);   // (radius queries ask for cell >= radius: 27 cells cover the ball)
         int nx, ny, nz;
         while (true) {
@@ -333,9 +349,13 @@ __global__ __launch_bounds__(PB) void k_grid_query(int m, int b, const float *__
 // read 64 at a time, accepted ones (as-written fp32 distance: same values as the scan) are appended to an LDS list, and the
 // nsample smallest INDICES are selected by rank counting (indices are unique), which also puts them in index order.  A query
 // whose ball holds more than RQ_CAP points falls back to the in-order scan of its scene inside the same wave.
+// PER_SCENE: the radius of the query's scene comes from radii[scene] (pdf_radius_neighbors_self_adaptive: k_grid_setup wrote it) instead of
+// the scalar; everything else is the one kernel.
 constexpr int RQ_WAVES = 4, RQ_CAP = 1024;
 
-__global__ __launch_bounds__(64 * RQ_WAVES) void k_grid_radius_self(int n, int b, int nsample, float radius, const float *__restrict__ xyz,
+template <bool PER_SCENE>
+__global__ __launch_bounds__(64 * RQ_WAVES) void k_grid_radius_self(int n, int b, int nsample, float radius, const float *__restrict__ radii,
+                                                                    const float *__restrict__ xyz,
                                                                     const int *__restrict__ offset, const SceneGrid *__restrict__ grids,
                                                                     const unsigned *__restrict__ cell_start, const float4 *__restrict__ sorted,
                                                                     int *__restrict__ idx, float *__restrict__ dist2) {
@@ -349,6 +369,7 @@ __global__ __launch_bounds__(64 * RQ_WAVES) void k_grid_radius_self(int n, int b
     const int sc = scene_of(q, offset, b);
     const SceneGrid g = grids[sc];
     const float qx = xyz[3 * (size_t)q], qy = xyz[3 * (size_t)q + 1], qz = xyz[3 * (size_t)q + 2];
+    if (PER_SCENE) radius = radii[sc];
     const float r2 = radius * radius;
     const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny), cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
     int cnt = 0;   // wave-uniform
@@ -438,7 +459,7 @@ static int knn_grid_build(int n, const float *xyz, const int *offset, int b, voi
     // cell size: `ppc` points per cell if the points filled the bounding box (they lie on surfaces, so occupied cells hold more)
     static const float ppc_env = [] { const char *v = getenv("PDFOPS_KNN_PPC"); return v ? (float)atof(v) : 0.f; }();
     const float ppc = ppc_env > 0.f ? ppc_env : 1.0f;   // measured on 12 x 100k-point scenes: 1 beats 4 by 25 % at level 1, equal below
-    kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, ppc, 0.f);
+    kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, ppc, 0.f, nullptr, 0.f, 0.f);
     kg::k_grid_hist<<<pdf_divup(n, kg::PB), kg::PB, 0, s>>>(n, b, xyz, offset, grids, cell_start, cell_of);
     kg::k_grid_scan<<<b, 1024, 0, s>>>(grids, cell_start);
     kg::k_grid_scatter<<<pdf_divup(n, kg::PB), kg::PB, 0, s>>>(n, xyz, cell_of, cell_start, cursor, sorted);
@@ -529,14 +550,12 @@ __global__ __launch_bounds__(256) void k_zero_words(unsigned *__restrict__ p, si
 }
 }  // namespace kg
 
-// Fixed-radius neighbour table of a batch with itself: idx (n, nsample) = the first nsample points of the query's scene, in index
-// order, within `radius` (the query included), -1 padded; dist2 = squared distances (1e10 padded).  Same results as
+// Neighbour table of a batch with itself within a radius: idx (n, nsample) = the first nsample points of the query's scene, in index
+// order, within the radius (the query included), -1 padded; dist2 = squared distances (1e10 padded).  Same results as
 // pdf_random_ball_query with order = identity and min_radius = 0.  Workspace: pdf_knn_workspace_bytes(b, n, 0).
-extern "C" int pdf_radius_neighbors_self(int n, int nsample, float radius, const float *xyz, const int *offset, int b, int *idx,
-                                         float *dist2, void *workspace, long workspace_bytes, void *stream) {
-    if (n == 0) return PDF_OK;
-    if (n < 0 || b < 1 || b > 64 || !xyz || !offset || !idx || !dist2 || !(radius > 0.f)) return PDF_ERR_BAD_ARG;
-    if (nsample < 1 || nsample > kg::RQ_CAP) return PDF_ERR_NSAMPLE;
+// radii == null: `radius` for every scene; else the scene's adaptive radius (k_grid_setup), written to radii (b).
+static int radius_neighbors_self(int n, int nsample, float radius, float *radii, float divisor, float pad, const float *xyz, const int *offset,
+                                 int b, int *idx, float *dist2, void *workspace, long workspace_bytes, void *stream) {
     const kg::Layout L = kg::make_layout(b, n, 0);
     if (!workspace || workspace_bytes < (long)L.total) return PDF_ERR_BAD_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -553,10 +572,32 @@ extern "C" int pdf_radius_neighbors_self(int n, int nsample, float radius, const
         const size_t words = (size_t)(L.cell_of - L.cell_start) / 4;
         kg::k_zero_words<<<pdf_divup((long)words, 1024), 256, 0, s>>>(reinterpret_cast<unsigned *>(ws + L.cell_start), words);
     }
-    kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, 1.0f, radius * 1.0001f);   // cell >= radius
+    if (radii) kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, 1.0f, 0.f, radii, divisor, pad);   // cell >= the scene's radius
+    else kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, 1.0f, fmaxf(radius, kg::RQ_MIN_REACH) * 1.0001f, nullptr, 0.f, 0.f);   // cell >= radius
     kg::k_grid_hist<<<pdf_divup(n, kg::PB), kg::PB, 0, s>>>(n, b, xyz, offset, grids, cell_start, cell_of);
     kg::k_grid_scan<<<b, 1024, 0, s>>>(grids, cell_start);
     kg::k_grid_scatter<<<pdf_divup(n, kg::PB), kg::PB, 0, s>>>(n, xyz, cell_of, cell_start, cursor, sorted);
-    kg::k_grid_radius_self<<<pdf_divup(n, kg::RQ_WAVES), 64 * kg::RQ_WAVES, 0, s>>>(n, b, nsample, radius, xyz, offset, grids, cell_start, sorted, idx, dist2);
+    const int grid = pdf_divup(n, kg::RQ_WAVES), block = 64 * kg::RQ_WAVES;
+    if (radii) kg::k_grid_radius_self<true><<<grid, block, 0, s>>>(n, b, nsample, 0.f, radii, xyz, offset, grids, cell_start, sorted, idx, dist2);
+    else kg::k_grid_radius_self<false><<<grid, block, 0, s>>>(n, b, nsample, radius, nullptr, xyz, offset, grids, cell_start, sorted, idx, dist2);
     return pdf_launch_status();
+}
+
+extern "C" int pdf_radius_neighbors_self(int n, int nsample, float radius, const float *xyz, const int *offset, int b, int *idx,
+                                         float *dist2, void *workspace, long workspace_bytes, void *stream) {
+    if (n == 0) return PDF_OK;
+    if (n < 0 || b < 1 || b > 64 || !xyz || !offset || !idx || !dist2 || !(radius > 0.f)) return PDF_ERR_BAD_ARG;
+    if (nsample < 1 || nsample > kg::RQ_CAP) return PDF_ERR_NSAMPLE;
+    return radius_neighbors_self(n, nsample, radius, nullptr, 0.f, 0.f, xyz, offset, b, idx, dist2, workspace, workspace_bytes, stream);
+}
+
+// The same table with one radius PER SCENE, derived on the device from the scene's extents (no host read of the coordinates: the table
+// stays inside a captured step): r_s = min over the axes of ((max - min) + pad) / divisor in fp32 -- with divisor 16, pad 1e-6 what
+// ((c.max(0)[0] - c.min(0)[0] + 1e-6) / 16).min() gives, pointpdf_v1m1_base.py:137-140 (adaptive_radius=True).  radii (b) receives r_s.
+extern "C" int pdf_radius_neighbors_self_adaptive(int n, int nsample, float divisor, float pad, const float *xyz, const int *offset, int b,
+                                                  int *idx, float *dist2, float *radii, void *workspace, long workspace_bytes, void *stream) {
+    if (n == 0) return PDF_OK;   // (nothing is launched: radii stays as it is)
+    if (n < 0 || b < 1 || b > 64 || !xyz || !offset || !idx || !dist2 || !radii || !(divisor > 0.f) || !(pad >= 0.f)) return PDF_ERR_BAD_ARG;
+    if (nsample < 1 || nsample > kg::RQ_CAP) return PDF_ERR_NSAMPLE;
+    return radius_neighbors_self(n, nsample, 0.f, radii, divisor, pad, xyz, offset, b, idx, dist2, workspace, workspace_bytes, stream);
 }

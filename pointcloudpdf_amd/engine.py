@@ -44,12 +44,17 @@ ST_V1M1_BACKBONE = dict(  # configs/s3dis/openseg-st-v1m1-0-origin-pointpdf-v1m1
     prev_grid_size=0.04, sigma=1.0, stem_transformer=True, kp_ball_radius=0.04 * 2.5, kp_max_neighbor=34)
 
 
+def _cfg_get(cfg, key, default=None):
+    """A config section by dict or attribute access (the reference's Config object, a plain dict): ``testing._cfg_get``."""
+    return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
+
+
 class OpenSegStep(nn.Module):
     def __init__(self, backbone="PointTransformer-Seg50", in_channels=6, num_classes=13, loss_weight=0.1,
                  start_epoch=0, pseudo_mask_fn=default_pseudo_mask):
         """``backbone``: a registered PointTransformer-Seg* name (PT-v1 + PDF U-decoder, BASELINE configs 2-4) or "ST-v1m1"
-        (StratifiedTransformer + ST-v1m1-Recognizer with the reference's S3DIS settings, BASELINE config 5)."""
-        super().__init__()
+        (StratifiedTransformer + ST-v1m1-Recognizer with the reference's S3DIS settings, BASELINE config 5).
+        ``OpenSegStep.from_config(cfg)`` / ``build_open_seg_step(cfg)`` build the step from a reference config instead."""
         from . import stratified  # noqa: F401  (registers ST-v1m1 / ST-v1m1-Recognizer)
 
         ce = [dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1)]
@@ -59,16 +64,75 @@ class OpenSegStep(nn.Module):
         else:
             bb = dict(type=backbone, in_channels=in_channels, num_classes=num_classes)
             rec, hooks = dict(type="PointTransformer-Recognizer"), PT_V1_HOOKS
-        self.model = MODELS.build(dict(type="DefaultSegmentor", backbone=bb, criteria=ce))
-        self.recognizer = RECOGNIZER.build(dict(type="PointPdf-v1m1", recognizer=rec,
-                                                criteria=ce, loss_weight=loss_weight, step_loss_weight=False,
-                                                num_classes=num_classes, start_epoch=start_epoch,
-                                                pseudo_mask_fn=pseudo_mask_fn))
-        self.hooks = BaseModelHook(hooks, clone_tensor=True, exclude_clone={"backbone": ["forward_output"]})
+        model = MODELS.build(dict(type="DefaultSegmentor", backbone=bb, criteria=ce))
+        recognizer_ = RECOGNIZER.build(dict(type="PointPdf-v1m1", recognizer=rec,
+                                            criteria=ce, loss_weight=loss_weight, step_loss_weight=False,
+                                            num_classes=num_classes, start_epoch=start_epoch,
+                                            pseudo_mask_fn=pseudo_mask_fn))
+        self._assemble(model, recognizer_, BaseModelHook(hooks, clone_tensor=True, exclude_clone={"backbone": ["forward_output"]}), start_epoch)
+
+    def _assemble(self, model, recognizer_, hooks, epoch):
+        """The ONE initialiser of the step, behind ``__init__`` and ``from_config`` alike: the built segmentor, the built recognizer, the hook
+        tap between them, and the recognizer's state at ``epoch``.  Every attribute of a step is set here."""
+        nn.Module.__init__(self)
+        self.model = model
+        self.recognizer = recognizer_
+        self.hooks = hooks
         self.hooks.set_model(self.model)
         self.recognizer.model_hooks = self.hooks
-        self.recognizer.set_epoch(start_epoch)
-        self.recognizer.trigger_operation()  # release the U-decoder parameters before DDP sees them
+        self.recognizer.set_epoch(epoch)
+        if hasattr(self.recognizer, "trigger_operation"):   # (MaxProbability has no parameters to freeze or release)
+            self.recognizer.trigger_operation()  # release the U-decoder parameters before DDP sees them
+
+    @classmethod
+    def from_config(cls, cfg):
+        """The step of a reference config (configs/*/openseg-*.py; dict or attribute access): ``cfg.model`` -- a ``DefaultSegmentor`` section
+        with any registered backbone -- ``cfg.recognizer`` -- ``PointPdf-v1m1``, whose pseudo-label pass ``PointPdfV1`` builds from the
+        section's own arguments (adaptive_radius included), or ``MaxProbability`` (method "msp" / "max_logits": no recognizer loss, no
+        recognizer parameters) -- and ``cfg.model_hooks`` -- a ``ModelHook`` section (``hook_config`` / ``exclude_clone`` values a string or a
+        list; a hook on a module the model does not have is dropped with one logged line; without the section: ``PT_V1_HOOKS`` /
+        ``ST_V1M1_HOOKS``).  Same module as the hand-wired ``OpenSegStep(...)``: same attribute and parameter names, same forward, the
+        recognizer at its ``start_epoch`` with its parameters released, so ``build_optimizer(cfg.optimizer, step, cfg.param_dicts)``,
+        ``TrainStep``, ``CapturedStep``, ``FlatGradAllReduce`` and ``testing.OpenSegTester(step, cfg)`` take it as it is."""
+        import logging
+
+        from . import stratified  # noqa: F401  (registers ST-v1m1 / ST-v1m1-Recognizer)
+
+        log = logging.getLogger(__name__)
+        model_cfg, rec_cfg, hook_cfg = _cfg_get(cfg, "model"), _cfg_get(cfg, "recognizer"), _cfg_get(cfg, "model_hooks")
+        if model_cfg is None or rec_cfg is None:
+            raise KeyError("build_open_seg_step: the config needs a `model` and a `recognizer` section")
+        model_cfg, rec_cfg = dict(model_cfg), dict(rec_cfg)
+        # (the ScanNet / S3DIS PT-v1 recipes hand PointPdf-v1m1 a `use_existing_nn` that upstream's class does not take either)
+        if rec_cfg.get("type") == "PointPdf-v1m1" and rec_cfg.pop("use_existing_nn", None) is not None:
+            log.info("build_open_seg_step: recognizer argument `use_existing_nn` is not an argument of PointPdf-v1m1: dropped")
+        model = MODELS.build(model_cfg)
+        recognizer_ = RECOGNIZER.build(rec_cfg)
+        is_st = dict(_cfg_get(model_cfg, "backbone", {})).get("type") == "ST-v1m1"
+        if hook_cfg is None:
+            hook_cfg = dict(hook_config=ST_V1M1_HOOKS if is_st else PT_V1_HOOKS, exclude_clone={"backbone": ["forward_output"]})
+        hook_cfg = dict(hook_cfg)
+        if hook_cfg.pop("type", "ModelHook") != "ModelHook":
+            raise KeyError("build_open_seg_step: `model_hooks` must be a ModelHook section")
+        as_list = lambda v: [v] if isinstance(v, str) else list(v)
+        # (the ST-v1m1 recipes spell hook_config `register_module_name`)
+        wanted = hook_cfg.pop("hook_config", None) or hook_cfg.pop("register_module_name", None) or {}
+        present = {name for name, _ in model.named_modules()}
+        missing = sorted(k for k in wanted if k not in present)
+        if missing:   # e.g. "backbone.upsamples.3" of the ST-v1m1 recipes: the backbone has three upsampling stages
+            log.warning("build_open_seg_step: no such module, hook dropped: %s", ", ".join(missing))
+        hooks = BaseModelHook({k: as_list(v) for k, v in wanted.items() if k in present},
+                              clone_tensor=hook_cfg.pop("clone_tensor", True),
+                              exclude_clone={k: as_list(v) for k, v in (hook_cfg.pop("exclude_clone", None) or {}).items()})
+        step = cls.__new__(cls)
+        step._assemble(model, recognizer_, hooks, getattr(recognizer_, "start_epoch", 0))
+        return step
+
+    @property
+    def prepass_plan(self):
+        """What the recognizer's pseudo-label pass asks of the coordinate pre-pass (``GroupedGeometryLoader(loader, group=...,
+        **step.prepass_plan)`` / ``Geometry.precompute(**step.prepass_plan)``): its radius table, or nothing."""
+        return dict(getattr(getattr(self.recognizer, "pseudo_mask_fn", None), "prepass_plan", None) or {})
 
     def forward(self, batch):
         input_dict = dict(batch)
@@ -82,6 +146,11 @@ class OpenSegStep(nn.Module):
             loss = loss + rec["loss"]
         return dict(loss=loss, model_loss=out["loss"].detach(), recognizer_loss=rec.get("loss", loss.new_zeros(())).detach(),
                     score=rec["score"].detach())
+
+
+def build_open_seg_step(cfg):
+    """``OpenSegStep.from_config(cfg)``: the training step of a reference open-world config, next to ``build_optimizer`` / ``build_scheduler``."""
+    return OpenSegStep.from_config(cfg)
 
 
 class IncrSegStep(nn.Module):

@@ -265,8 +265,10 @@ class Geometry:
     def radius(self, radius, max_neighbor):
         """Radius table of the level-0 points with themselves: (N, max_neighbor) int32 GLOBAL rows, -1 padded, the point itself included
         (``pseudo_label.radius_neighbors(raw=True)``) -- the neighbour table of the PDF pseudo-label pass (pointpdf_v1m1_base.py:131-137).
-        It reads coordinates only, so it belongs to the pre-pass like the kNN tables (0.66 ms of the step at 2 x 150k points otherwise)."""
-        key = ("radius", float(radius), int(max_neighbor))
+        It reads coordinates only, so it belongs to the pre-pass like the kNN tables (0.66 ms of the step at 2 x 150k points otherwise).
+        ``radius="adaptive"``: every scene within its own radius (``pseudo_label.adaptive_radii``); the query works per scene, so the
+        table of a group of batches holds each batch's own table."""
+        key = self._radius_key(radius, max_neighbor)
         if key not in self._memo:
             from .pseudo_label import radius_neighbors
 
@@ -275,7 +277,11 @@ class Geometry:
 
     def radius_cached(self, radius, max_neighbor):
         """The table ``radius()`` made ahead of the step, or None (the caller then runs the query itself)."""
-        return self._memo.get(("radius", float(radius), int(max_neighbor)))
+        return self._memo.get(self._radius_key(radius, max_neighbor))
+
+    @staticmethod
+    def _radius_key(radius, max_neighbor):
+        return ("radius", radius if isinstance(radius, str) else float(radius), int(max_neighbor))
 
     def memo_size(self):
         """Number of memoised geometry ops (FPS + kNN + interpolation tables)."""

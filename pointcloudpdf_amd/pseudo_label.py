@@ -35,12 +35,48 @@ import torch
 from . import _native
 
 
+ADAPTIVE = "adaptive"   # the `radius` of the reference's adaptive_radius=True: one radius per scene, from the scene's extents
+
+
+def _radius_arg(radius):
+    """The ``radius`` argument in its canonical form: the string "adaptive" or a float."""
+    if isinstance(radius, str):
+        if radius != ADAPTIVE:
+            raise ValueError(f"radius: a number or '{ADAPTIVE}', got {radius!r}")
+        return ADAPTIVE
+    return float(radius)
+
+
+def adaptive_radii(coord, offset):
+    """pointpdf_v1m1_base.py:137-140 per scene: ``((c.max(0)[0] - c.min(0)[0] + 1e-6) / 16).min()`` -> (B,) tensor of coord's dtype.
+    Reads ``offset`` on the host: the CPU / oracle path and the tests' truth (the HIP backend derives the same values on the device)."""
+    ends = [int(v) for v in offset.tolist()]
+    extent = lambda c: c.max(0)[0] - c.min(0)[0] if c.shape[0] else c.new_zeros(3)   # (a scene without points: extent 0, as the kernel)
+    return torch.stack([((extent(c) + 1e-6) / 16).min() for c in (coord[s:e] for s, e in zip([0] + ends[:-1], ends))])
+
+
 def radius_neighbors(coord, offset, radius, max_neighbor, raw=False):
     """-> (N, max_neighbor) int64 neighbour ids (global rows, the point itself included), -1 padded.  ``raw``: the backend's int32 table
-    as it is (what ``get_pseudo_mask_static`` reads; saves two passes over 8 N max_neighbor bytes)."""
+    as it is (what ``get_pseudo_mask_static`` reads; saves two passes over 8 N max_neighbor bytes).  ``radius``: metres, or "adaptive":
+    every scene searched within its own ``adaptive_radii`` (the reference's adaptive_radius=True)."""
     be = _native.backend_for(coord)
     off = offset.int().contiguous()
-    if hasattr(be, "radius_neighbors_self"):       # HIP: 27 grid cells around every point instead of the whole scene (same results)
+    if _radius_arg(radius) == ADAPTIVE:
+        if hasattr(be, "radius_neighbors_self_adaptive"):   # HIP: the radii come out of the grid setup's extents, no host read
+            idx = be.radius_neighbors_self_adaptive(int(max_neighbor), coord.contiguous(), off)[0]
+        else:
+            ends = [int(v) for v in off.tolist()]
+            parts = []
+            for s, e, r in zip([0] + ends[:-1], ends, adaptive_radii(coord, off).tolist()):
+                if e == s:
+                    continue
+                c = coord[s:e].contiguous()
+                o1 = torch.tensor([e - s], dtype=torch.int32, device=coord.device)
+                order = torch.arange(e - s, dtype=torch.int32, device=coord.device)
+                i, _ = be.ball_query(int(max_neighbor), float(r), 0.0, c, c, o1, o1, order=order)
+                parts.append(torch.where(i >= 0, i + s, i))
+            idx = torch.cat(parts) if parts else torch.empty((0, int(max_neighbor)), dtype=torch.int32, device=coord.device)
+    elif hasattr(be, "radius_neighbors_self"):       # HIP: 27 grid cells around every point instead of the whole scene (same results)
         idx, _ = be.radius_neighbors_self(int(max_neighbor), float(radius), coord.contiguous(), off)
     else:
         order = torch.arange(coord.shape[0], dtype=torch.int32, device=coord.device)   # identity permutation: index order
@@ -550,7 +586,9 @@ def get_pseudo_mask(coord, seg_logits, offset, radius=0.1, max_neighbor=64, neig
 def make_pseudo_mask_fn(radius=0.1, max_neighbor=64, **kw):
     """A ``pseudo_mask_fn(coord, seg_logits, offset)`` for ``recognizer.PointPdfV1`` / ``engine.OpenSegStep`` built from the
     recognizer section of configs/scannet/openseg-pt-v1-0-pointpdf-v1m1-base.py:40-58 (kp_ball_radius, kp_max_neighbor,
-    condition_from, beta, seed_from, seed_range, num_seed, slide_window)."""
+    condition_from, beta, seed_from, seed_range, num_seed, slide_window).  ``radius="adaptive"`` is the section's adaptive_radius=True:
+    the per-scene radius of ``adaptive_radii`` in place of kp_ball_radius.  (``PointPdfV1`` builds this itself from its kp_* arguments.)"""
+    radius = _radius_arg(radius)
     def fn(coord, seg_logits, offset, offset_host=None, geometry=None):
         # the neighbour table from the batch's coordinate pre-pass when it made one (geometry.Geometry.radius: `prepass_plan` below)
         table = geometry.radius_cached(radius, max_neighbor) if geometry is not None and hasattr(geometry, "radius_cached") else None
@@ -560,7 +598,7 @@ def make_pseudo_mask_fn(radius=0.1, max_neighbor=64, **kw):
                                offset_host=offset_host, **kw)
 
     fn.accepts_geometry = True      # (PointPdfV1 hands over input_dict["pdf_geometry"])
-    fn.prepass_plan = dict(radius=(float(radius), int(max_neighbor)))   # -> engine.GroupedGeometryLoader(..., **fn.prepass_plan) / Geometry.precompute
+    fn.prepass_plan = dict(radius=(radius, int(max_neighbor)))   # -> engine.GroupedGeometryLoader(..., **fn.prepass_plan) / Geometry.precompute
     fn.accepts_offset_host = True   # (PointPdfV1 hands the host copy of the scene ends over when the batch carries one: no read of `offset`)
     # device tensors take the sync-free form: the pass can be recorded into the step's graph (engine.CapturedStep captures ONE graph then)
     fn.capturable = os.environ.get("PDFOPS_PL_STATIC", "1") != "0" and kw.get("prune", "auto") in ("auto", "hip") and kw.get("generator") is None

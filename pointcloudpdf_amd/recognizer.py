@@ -3,8 +3,9 @@
 * ``PTRecognizer`` -- the PDF **U-decoder** uncertainty head, pointcept/recognizers/recognizer_model/pt_v1.py:8-44
   (registered as ``PointTransformer-Recognizer``; parameter names ``dec{1..5}.linear{1,2}``, ``confidence``).
 * ``PointPdfV1`` -- forward/score/loss part of pointcept/recognizers/ours/pointpdf_v1m1_base.py:72-116 and
-  ``trigger_operation`` (:384-398).  The pseudo-label pass (:118-382; third-party ball query + CPU graph code) is
-  a "next" row of the scope table: a ``pseudo_mask_fn(coord, seg_logits, offset) -> bool mask`` can be plugged in.
+  ``trigger_operation`` (:384-398).  The pseudo-label pass (:118-382) is ``pseudo_label.make_pseudo_mask_fn``: built here from the
+  config section's own arguments (kp_ball_radius or adaptive_radius, kp_max_neighbor, condition_from, beta, seed_from, seed_range,
+  num_seed, slide_window) unless a ``pseudo_mask_fn(coord, seg_logits, offset) -> bool mask`` is plugged in, which always wins.
 * ``MaxProbability`` -- MSP / max-logit baselines, pointcept/recognizers/max_probability/max_probability_v1m1_base.py:7-32.
 """
 import os
@@ -67,6 +68,12 @@ class PointPdfV1(nn.Module):
         self.seed_from, self.seed_range, self.num_seed = seed_from, seed_range, num_seed
         self.slide_window, self.adaptive_radius = slide_window, adaptive_radius
         self.softmax_score = softmax_score
+        if pseudo_mask_fn is None and kp_max_neighbor is not None and (adaptive_radius or kp_ball_radius is not None):
+            from .pseudo_label import make_pseudo_mask_fn
+
+            given = dict(condition_from=condition_from, beta=beta, seed_from=seed_from, seed_range=seed_range, num_seed=num_seed)
+            pseudo_mask_fn = make_pseudo_mask_fn(radius="adaptive" if adaptive_radius else kp_ball_radius, max_neighbor=kp_max_neighbor,
+                                                 slide_window=slide_window, **{k: v for k, v in given.items() if v is not None})
         self.pseudo_mask_fn = pseudo_mask_fn
         # (off by default: measured inconclusive on a loaded pod -- 38.7 vs 42.1 ms per step averaged over three traced runs each, 43.6 vs
         # 42.1 over four untraced ones, profiles/r04_pl_side_stream_ab.txt; PDFOPS_PL_SIDE_STREAM=1 turns it on)
@@ -81,8 +88,8 @@ class PointPdfV1(nn.Module):
     def get_pseudo_mask(self, coord, seg_logits, offset, offset_host=None, geometry=None):
         if self.pseudo_mask_fn is None:
             raise NotImplementedError(
-                "PDF pseudo-label pass (pointpdf_v1m1_base.py:118-382) is row f-2 of the scope table; "
-                "pass pseudo_mask_fn=... to supply the mask"
+                "PDF pseudo-label pass (pointpdf_v1m1_base.py:118-382, row f-2 of the scope table): this recognizer was built without "
+                "kp_ball_radius (or adaptive_radius) / kp_max_neighbor and without pseudo_mask_fn=..., so it has no pass to run"
             )
         with torch.no_grad():
             ready = getattr(self, "_logits_ready", None)
