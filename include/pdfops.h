@@ -42,8 +42,9 @@ extern "C" {
  * 5 = round 5: pdf_wa_* (atomic-free window-attention backward, fused logits), pdf_layernorm_*, pdf_region_* / *_dev (sync-free pseudo-label pass) added;
  * 7 = pdf_adam_step / pdf_adam_grad_unscale added (no existing parameter list changed);
  * 8 = pdf_fragment_bounds / pdf_fragment_gather / pdf_fragment_vote added (no existing parameter list changed);
- * 9 = pdf_radius_neighbors_self_adaptive added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 9
+ * 9 = pdf_radius_neighbors_self_adaptive added (no existing parameter list changed);
+ * 10 = pdf_lovasz_workspace_bytes / pdf_lovasz_forward / pdf_lovasz_backward added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 10
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -387,6 +388,21 @@ long pdf_incr_kl_workspace_floats(void);
 int pdf_incr_kl_forward(long n, int cs, int ct, const float *student, const float *teacher, const long *labels, long ignore, float inv_tp,
                         float inv_tt, float *grad, float *acc, float *loss, void *stream);
 int pdf_incr_kl_backward(long n, int cs, const float *dgrad, const float *acc, const float *gy, float *grad_out, void *stream);
+
+/* Lovasz-softmax, multiclass, over the whole batch (pointcept/models/losses/lovasz.py:89-164, 241-257 with per_image=False): logits
+ * (n, c <= 64) fp32, target (n) int64.  P = softmax(logits); for every class that occurs among the rows whose target != ignore (and,
+ * with class_mask, whose mask byte is non-zero): e = |fg - P[:, class]| sorted descending (equal errors keep ascending row order: a
+ * stable sort, so the subgradient is defined and reproducible), loss_class = sum_i e_i (J_i - J_{i-1}) with the Jaccard index J_i formed
+ * from integer counts in double; loss[0] = mean over those classes (added in ascending class order), loss[1] = their number (0 when
+ * every row is ignored: loss 0, gradient 0).  A target that is neither `ignore` nor in [0, c) makes the loss NaN.  prob (n*c) receives
+ * P, dlogits (n*c) the finished d loss / d logits.  workspace: pdf_lovasz_workspace_bytes(n, c) bytes, every byte written before it is
+ * read (nothing to zero, no atomics, bit-reproducible).  n < 1, n >= 2^31 - 1 or c < 1: PDF_ERR_BAD_ARG; c > 64: PDF_ERR_UNSUPPORTED.
+ * Backward: grad_out = dlogits * gy[0] * scale; dlogits is only read, so the node can be differentiated more than once; grad_out may
+ * alias it. */
+long pdf_lovasz_workspace_bytes(long n, int c);
+int pdf_lovasz_forward(long n, int c, const float *logits, const long *target, long ignore, const unsigned char *class_mask, float *prob,
+                       float *dlogits, float *loss, void *workspace, void *stream);
+int pdf_lovasz_backward(long n, int c, const float *dlogits, const float *gy, float scale, float *grad_out, void *stream);
 
 /* Per-scene sums of the relative coordinates rel = xyz[idx[i, j]] - xyz[i] of a SELF neighbour table (rows with idx < 0: rel = 0):
  * out (b, 9) double = [Sx Sy Sz | Mxx Mxy Mxz Myy Myz Mzz], WRITTEN (every workgroup lies inside one scene and stores its nine sums

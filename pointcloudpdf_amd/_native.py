@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 9   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 10   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -681,6 +681,12 @@ class HipBackend(CBackend):
                                             c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_incr_kl_backward.restype = c_int
         lib.pdf_incr_kl_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.pdf_lovasz_workspace_bytes.restype = c_long
+        lib.pdf_lovasz_workspace_bytes.argtypes = [c_long, c_int]
+        lib.pdf_lovasz_forward.restype = c_int
+        lib.pdf_lovasz_forward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.pdf_lovasz_backward.restype = c_int
+        lib.pdf_lovasz_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p]
         lib.pdf_knn_rel_moments.restype = c_int
         lib.pdf_knn_rel_moments.argtypes = [c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_knn_rel_moments_ws_doubles.restype = c_long

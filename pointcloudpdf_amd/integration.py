@@ -44,3 +44,13 @@ def register_into_pointcept(force=True):
         PC_HOOKS.register_module(name="ModelHook", force=force, module=MODELHOOKS.get("ModelHook"))
     except ImportError:
         pass
+
+
+def register_losses_into_pointcept(force=True):
+    """Register ``LovaszLoss`` (losses.py: the capturable HIP pass on the device) under the reference's name in a live pointcept
+    install's ``pointcept.models.losses.builder.LOSSES``, so that its own ``build_criteria`` builds ours."""
+    from pointcept.models.losses.builder import LOSSES as PC_LOSSES  # noqa: import error = pointcept not importable
+    from . import losses  # noqa: F401  (fills the registry)
+    from .registry import LOSSES
+
+    PC_LOSSES.register_module(name="LovaszLoss", force=force, module=LOSSES.get("LovaszLoss"))

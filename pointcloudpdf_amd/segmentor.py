@@ -68,6 +68,9 @@ class _FusedCE(torch.autograd.Function):
         return out, None, None
 
 
+from . import losses  # noqa: E402,F401  (registers LovaszLoss: LOSSES is complete once this module is imported)
+
+
 class Criteria:
     """losses/builder.py:13-27: sum of the configured losses; an empty list returns the prediction itself."""
 
