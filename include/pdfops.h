@@ -43,8 +43,9 @@ extern "C" {
  * 7 = pdf_adam_step / pdf_adam_grad_unscale added (no existing parameter list changed);
  * 8 = pdf_fragment_bounds / pdf_fragment_gather / pdf_fragment_vote added (no existing parameter list changed);
  * 9 = pdf_radius_neighbors_self_adaptive added (no existing parameter list changed);
- * 10 = pdf_lovasz_workspace_bytes / pdf_lovasz_forward / pdf_lovasz_backward added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 10
+ * 10 = pdf_lovasz_workspace_bytes / pdf_lovasz_forward / pdf_lovasz_backward added (no existing parameter list changed);
+ * 11 = pdf_openset_metrics_workspace_bytes / pdf_openset_metrics added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 11
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -403,6 +404,25 @@ long pdf_lovasz_workspace_bytes(long n, int c);
 int pdf_lovasz_forward(long n, int c, const float *logits, const long *target, long ignore, const unsigned char *class_mask, float *prob,
                        float *dlogits, float *loss, void *workspace, void *stream);
 int pdf_lovasz_backward(long n, int c, const float *dlogits, const float *gy, float scale, float *grad_out, void *stream);
+
+/* Open-set metrics of n rows in one pass (pointcept/utils/misc.py:55-87; csrc/openset_metrics.hip): the class histograms of
+ * intersection_and_union_gpu as exact counts and AUPR / AUROC as sklearn's average_precision_score / roc_auc_score define them.
+ * Exactly one of logits (n, c) fp32 and pred (n) int64 is given; a prediction from logits is the lowest index among the row's maximal
+ * values, a NaN counting as maximal (torch.max(1)[1]).  target (n) int64; rows with target == ignore are dropped.  hist (3, k) int64 =
+ * intersection | union | target over the classes [0, k): a prediction or a label outside [0, k) is left out of its own histogram only.
+ * score (n) fp32 or NULL; unknown: k bytes, 1 = the class id counts as positive (NULL: no class does).  record (4) double = [aupr, auroc,
+ * n_pos, n_neg] over the kept rows: aupr = sum over the groups of equal score, descending, of (tp_g - tp_{g-1}) / n_pos * tp_g / (tp_g +
+ * fp_g), summed in double in a fixed order; auroc = S / (2 n_pos n_neg) with the INTEGER S = sum_g (fp_g - fp_{g-1}) (tp_g + tp_{g-1})
+ * (the tie-grouped trapezoid, independent of summation order).  -0.0 and +0.0 are one score, +-inf ordinary values.  n_pos == 0 (also:
+ * no kept row): aupr = auroc = NaN; n_neg == 0: auroc = NaN; a NaN score on a kept row: aupr = auroc = NaN (the counts stay); score ==
+ * NULL: record = NaN, NaN, 0, 0 and only the histogram kernels run.  Every element of hist and record is written.  workspace:
+ * pdf_openset_metrics_workspace_bytes(n, c) bytes (the size depends on n alone; c is the logits' width or 0), 8-byte aligned, every byte
+ * written before it is read (nothing to zero, no float atomics, bit-reproducible, capturable).  n < 1, n >= 2^31 - 1, k < 1, both or
+ * neither of logits / pred, c < 1 with logits, a NULL target / hist / record / workspace: PDF_ERR_BAD_ARG before any launch; k > 1024:
+ * PDF_ERR_UNSUPPORTED. */
+long pdf_openset_metrics_workspace_bytes(long n, int c);
+int pdf_openset_metrics(long n, int c, const float *logits, const long *pred, const float *score, const long *target, long ignore,
+                        const unsigned char *unknown, int k, long long *hist, double *record, void *workspace, void *stream);
 
 /* Per-scene sums of the relative coordinates rel = xyz[idx[i, j]] - xyz[i] of a SELF neighbour table (rows with idx < 0: rel = 0):
  * out (b, 9) double = [Sx Sy Sz | Mxx Mxy Mxz Myy Myz Mzz], WRITTEN (every workgroup lies inside one scene and stores its nine sums

@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 10   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 11   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -687,6 +687,11 @@ class HipBackend(CBackend):
         lib.pdf_lovasz_forward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_lovasz_backward.restype = c_int
         lib.pdf_lovasz_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p]
+        lib.pdf_openset_metrics_workspace_bytes.restype = c_long
+        lib.pdf_openset_metrics_workspace_bytes.argtypes = [c_long, c_int]
+        lib.pdf_openset_metrics.restype = c_int
+        lib.pdf_openset_metrics.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]
         lib.pdf_knn_rel_moments.restype = c_int
         lib.pdf_knn_rel_moments.argtypes = [c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_knn_rel_moments_ws_doubles.restype = c_long
@@ -1324,6 +1329,37 @@ class HipBackend(CBackend):
 
     def _stream(self):
         return c_void_p(raw_stream())
+
+    def openset_metrics(self, logits, pred, score, target, ignore, unknown, k):
+        """-> (hist (3, k) int64: intersection | union | target, record (4) float64: aupr, auroc, n_pos, n_neg) on the inputs' device
+        (pdf_openset_metrics; csrc/openset_metrics.hip).  Exactly one of ``logits`` (n, c) float32 and ``pred`` (n) int64; ``score`` (n)
+        float32 or None; ``unknown``: (k) uint8 on the device or None.  No host read; every byte of the workspace is written before it is
+        read, so nothing is zeroed and a captured call holds no memset node."""
+        if (logits is None) == (pred is None):
+            raise ValueError("openset_metrics: exactly one of logits and pred")
+        x = logits if pred is None else pred
+        _check(x, torch.float32 if pred is None else torch.int64, "logits" if pred is None else "pred")
+        _check(target, torch.int64, "target")
+        if score is not None:
+            _check(score, torch.float32, "score")
+        if unknown is not None:
+            _check(unknown, torch.uint8, "unknown")
+            if unknown.numel() != k:
+                raise ValueError(f"openset_metrics: the unknown-class mask has {unknown.numel()} bytes for {k} classes")
+        n, c = x.shape[0], (x.shape[1] if pred is None else 0)
+        if target.numel() != n or (score is not None and score.numel() != n):
+            raise ValueError("openset_metrics: logits / pred, score and target must have one row count")
+        require_current_device(x, score, target, unknown)
+        hist = torch.empty((3, k), dtype=torch.int64, device=x.device)
+        record = torch.empty((4,), dtype=torch.float64, device=x.device)
+        ws = torch.empty((max(int(self.lib.pdf_openset_metrics_workspace_bytes(n, c)), 8),), dtype=torch.uint8, device=x.device)
+        rc = self.lib.pdf_openset_metrics(n, c, None if logits is None else logits.data_ptr(), None if pred is None else pred.data_ptr(),
+                                          None if score is None else score.data_ptr(), target.data_ptr(), int(ignore),
+                                          None if unknown is None else unknown.data_ptr(), int(k), hist.data_ptr(), record.data_ptr(),
+                                          ws.data_ptr(), self._stream())
+        if rc != 0:
+            raise PdfOpsError(f"pdf_openset_metrics failed with status {rc}")
+        return hist, record
 
     def rowlin(self, x, w, bias=None, coef=None, relu=False, transpose_w=False, out=None, accumulate=False, stats=False):
         """y = f(x) @ Wt + bias (see include/pdfops.h); x (n,k) with row stride x.stride(0); returns (y, partial|None)."""

@@ -8,6 +8,7 @@ derives from them: ``pred = votes.argmax(1)``, ``score = sum / count`` (0 where 
 convention).  ``fragment_inference`` is that loop, one fragment per forward.  The second half of the module is the tester proper:
 ``TestPipeline`` / ``SceneTester`` / ``OpenSegTester`` / ``IncrSegTester`` run a reference ``cfg.data.test`` dict on raw scenes with batched
 fragments, look-ahead geometry and an ordered, atomic-free batched vote (csrc/fragments.hip)."""
+import logging
 import os
 
 import numpy as np
@@ -68,6 +69,10 @@ def fragment_inference(segmentor, recognizer_score_fn, data, fragments, num_clas
 # Host tensors run a torch-op composition of the same steps (``_host_*`` below): that is how the host logic is tested without a GPU.
 # ================================================================================================================================
 from . import augment, data_path, evaluator, voxelize  # noqa: E402
+
+_LOG = logging.getLogger(__name__)
+_CODE_POS, _CODE_IGNORE = 1, 2          # OpenSegTester's all-points labels: 0 = negative, 1 = positive (unknown class), 2 = ignored
+_MAX_FUSED_ROWS = 2 ** 31 - 1           # rows of one pdf_openset_metrics call stay below this
 
 _FNV_OFFSET = 14695981039346656037 - (1 << 64)      # the uint64 constants of fnv_hash_vec as int64 bit patterns (int64 products wrap)
 _FNV_PRIME = 1099511628211
@@ -411,36 +416,40 @@ class _TesterBase:
         return st["segment"]
 
     def _scene(self, scene, result_dir, need_score):
-        """-> (pred, score, segment) as host arrays on the full-resolution scene."""
+        """-> (name, pred, score, segment) on the full-resolution scene as tensors on the tester's device.  Host copies are made for the
+        result files only; results reloaded from them are uploaded."""
         name = scene.get("name", "scene")
-        st = self.pipeline.prepare(scene, self.scene_tester.device)
+        dev = self.scene_tester.device
+        st = self.pipeline.prepare(scene, dev)
         pred_path = os.path.join(result_dir, f"{name}_pred.npy") if result_dir else None
         score_path = os.path.join(result_dir, f"{name}_score.npy") if result_dir else None
         if pred_path and os.path.isfile(pred_path) and (not need_score or os.path.isfile(score_path)):   # test.py:195-204
-            pred = np.load(pred_path)
-            score = np.load(score_path) if need_score else None
+            pred = torch.from_numpy(np.load(pred_path)).to(dev)
+            score = torch.from_numpy(np.load(score_path)).to(dev) if need_score else None
         else:
             votes, ssum, scnt, scored = self.scene_tester.vote(st)
-            pred = votes.max(1)[1].cpu().numpy()
-            score = (ssum / scnt.clamp(min=1.0)).cpu().numpy() if scored else None
+            pred = votes.max(1)[1]
+            score = ssum / scnt.clamp(min=1.0) if scored else None
             if pred_path:
-                np.save(pred_path, pred)
+                np.save(pred_path, pred.cpu().numpy())
                 if need_score and score is not None:
-                    np.save(score_path, score)
+                    np.save(score_path, score.cpu().numpy())
         segment = self._labels(st)
         if "inverse" in st:   # test.py:254-257 (the score follows the prediction back to the full-resolution scene)
-            inv = st["inverse"].cpu().numpy()
+            inv = st["inverse"]
             pred, score = pred[inv], (score[inv] if score is not None else None)
             segment = self._origin_labels(st)
-        return name, pred, score, segment.cpu().numpy()
+        return name, pred.long().contiguous(), (None if score is None else score.float().contiguous()), segment.long().contiguous()
 
     def _origin_labels(self, st):
         return st["origin_segment"]
 
-    def _histogram(self, pred, segment):
-        i, u, t = evaluator.intersection_and_union(torch.from_numpy(np.asarray(pred)), torch.from_numpy(np.asarray(segment)), self.dim_pred,
-                                                   self.ignore_index)
-        return i.double().numpy(), u.double().numpy(), t.double().numpy()
+    def _metrics(self, pred, score, segment, unknown_label=()):
+        """``evaluator.openset_metrics`` of one scene, read back at once -> (intersection, union, target (K) float64, record (4))."""
+        hist, rec = evaluator.openset_metrics(pred, score, segment, self.dim_pred, unknown_label, self.ignore_index)
+        flat = torch.cat([hist.reshape(-1).double(), rec]).cpu().numpy()
+        h = flat[:-4].reshape(3, -1)
+        return h[0], h[1], h[2], flat[-4:]
 
     @staticmethod
     def _result_dir(save_path):
@@ -498,35 +507,58 @@ class OpenSegTester(_TesterBase):
         self.unknown_label = [int(v) for v in _cfg_get(cfg, "unknown_label", [])]
         self.mask_known = np.ones(self.dim_pred, dtype=bool)
         self.mask_known[self.unknown_label] = False
+        dev = self.scene_tester.device
+        if dev.type == "cuda":   # the byte masks of the per-scene and the all-points call, uploaded once
+            self._unknown = evaluator.unknown_mask(self.dim_pred, self.unknown_label, dev)
+            self._unknown_code = evaluator.unknown_mask(2, [_CODE_POS], dev)
+        else:
+            self._unknown, self._unknown_code = self.unknown_label, [_CODE_POS]
+
+    def _codes(self, segment):
+        """One byte per point for the all-points figures: negative / positive / ignored."""
+        unknown = torch.as_tensor(self.unknown_label, dtype=segment.dtype, device=segment.device)
+        code = torch.isin(segment, unknown).to(torch.uint8) * _CODE_POS
+        return torch.where(segment == self.ignore_index, torch.full_like(code, _CODE_IGNORE), code)
 
     def test(self, scenes, save_path=None):
         result_dir = self._result_dir(save_path)
         k = self.mask_known
         isum, usum, tsum = (np.zeros(self.dim_pred) for _ in range(3))
-        auprs, aurocs, per_scene, all_score, all_segment = [], [], {}, [], []
+        auprs, aurocs, per_scene, all_score, all_code = [], [], {}, [], []
         for scene in scenes:
             name, pred, score, segment = self._scene(scene, result_dir, need_score=True)
-            i, u, t = self._histogram(pred, segment)
+            i, u, t, record = self._metrics(pred, score, segment, self._unknown)
             isum, usum, tsum = isum + i, usum + u, tsum + t
             cls = (u != 0) & k                                                         # test.py:268-279
             rec = dict(intersection=i, union=u, target=t,
                        mIoU=float(np.mean((i / (u + 1e-10))[cls])), allAcc=float(sum(i[cls]) / (sum(t[cls]) + 1e-10)),
                        running_mIoU=float(np.mean(isum[cls] / (usum[cls] + 1e-10))), running_mAcc=float(np.mean(isum[cls] / (tsum[cls] + 1e-10))))
-            aupr, auroc = evaluator.aupr_and_auroc(torch.from_numpy(score), torch.from_numpy(segment), self.unknown_label, self.ignore_index)
+            aupr, auroc = (float(record[0]), float(record[1])) if record[2] > 0 else (None, None)
             if aupr is not None:                                                       # test.py:281-294
                 auprs.append(aupr); aurocs.append(auroc)
             rec.update(aupr=aupr, auroc=auroc)
             per_scene[name] = rec
-            all_score.append(score); all_segment.append(segment)
+            all_score.append(score); all_code.append(self._codes(segment))             # 5 bytes per point stay on the device
         iou_class, acc_class = isum / (usum + 1e-10), isum / (tsum + 1e-10)             # test.py:405-411
         out = dict(mIoU=float(np.mean(iou_class[k])), mAcc=float(np.mean(acc_class[k])), allAcc=float(sum(isum[k]) / (sum(tsum[k]) + 1e-10)),
                    iou_class=iou_class, acc_class=acc_class, intersection=isum, union=usum, target=tsum,
                    aupr=float(np.mean(auprs)) if auprs else float("nan"), auroc=float(np.mean(aurocs)) if aurocs else float("nan"), scenes=per_scene)
         if all_score:                                                                   # test.py:419-427
-            a, r = evaluator.aupr_and_auroc(torch.from_numpy(np.concatenate(all_score)), torch.from_numpy(np.concatenate(all_segment)),
-                                            self.unknown_label, self.ignore_index)
+            a, r = self._all_points(all_score, all_code)
             out.update(all_aupr=float("nan") if a is None else a, all_auroc=float("nan") if r is None else r)
         return out
+
+    def _all_points(self, scores, codes):
+        """AUPR / AUROC over every point of the split: one ``openset_metrics`` call over the concatenation (labels = the codes)."""
+        total = sum(int(c.shape[0]) for c in codes)
+        if total >= _MAX_FUSED_ROWS and codes[0].is_cuda:
+            _LOG.warning("OpenSegTester: %d points exceed one device pass (2^31 - 2 rows); all-points AUPR / AUROC on the host", total)
+            scores, codes = [s.cpu() for s in scores], [c.cpu() for c in codes]
+        score, code = torch.cat(scores), torch.cat(codes).long()
+        unknown = self._unknown_code if code.is_cuda else [_CODE_POS]
+        _, rec = evaluator.openset_metrics(code, score, code, 2, unknown, _CODE_IGNORE)
+        rec = rec.cpu().numpy()
+        return (float(rec[0]), float(rec[1])) if rec[2] > 0 else (None, None)
 
 
 class IncrSegTester(_TesterBase):
@@ -564,7 +596,7 @@ class IncrSegTester(_TesterBase):
         per_scene = {}
         for scene in scenes:
             name, pred, _, segment = self._scene(scene, result_dir, need_score=False)
-            i, u, t = self._histogram(pred, segment)
+            i, u, t, _ = self._metrics(pred, None, segment)
             isum, usum, tsum = isum + i, usum + u, tsum + t
             mask = u != 0                                                              # test.py:636-698
             iou = i / (u + 1e-10)
