@@ -1118,8 +1118,9 @@ class HipBackend(CBackend):
 
     # -- dense per-point Linear on the matrix cores (csrc/rowlin.hip) ---------------------------------------
     # -- libs/pointops2 window attention, backward: atomic-free segmented sums (csrc/window_attention_bwd.hip) ---------------------
-    # PDFOPS_WA_ATOMICS=1: the fp32-atomic launchers of rounds 1-4 (csrc/window_attention.hip) -- A/B and fallback for other shapes
-    wa_atomic_free = os.environ.get("PDFOPS_WA_ATOMICS", "0") != "1"
+    # False: the fp32-atomic launchers of csrc/window_attention.hip for every shape (the independent implementation the tests compare
+    # against; other shapes take them anyway)
+    wa_atomic_free = True
 
     def _wa_ok(self, d, L, *tensors):
         return self.wa_atomic_free and d == 16 and L <= 64 and all(t.data_ptr() % 16 == 0 for t in tensors)
@@ -1132,11 +1133,6 @@ class HipBackend(CBackend):
             order = None
         self._call("wa_segment_rows_ordered", n, h, d, L, seg_off, seg_edge, other, rel, w, X, c if ldx is None else int(ldx), float(xscale), table, out,
                    c if ldo is None else int(ldo), float(oscale), order)
-
-    wa_window_order = os.environ.get("PDFOPS_WA_WINDOW_ORDER", "1") != "0"   # (A/B: 0 = owners in storage order)
-
-    def _wa_order(self, offsets):
-        return window_order_of(offsets) if self.wa_window_order else None
 
     def _wa_permute(self, w, edge):
         """w (M, h) float32 -> w[edge] (torch's index_select takes 25-95 us for these 12-96-byte rows; this is one pass at copy speed)"""
@@ -1283,11 +1279,9 @@ class HipBackend(CBackend):
     # The whole attention core of WindowAttention.forward (stratified_transformer_v1m1_origin.py:296-341) on the (N, 3 C) output of the
     # qkv Linear: q / k / v are read as column slices (no permute copy), the query scale rides on the kernels, and the backward writes
     # the three gradients into the slices of one (N, 3 C) buffer.
-    wa_core = os.environ.get("PDFOPS_WA_CORE", "1") != "0"   # (A/B: 0 = the model composes window_logits / softmax / step2 itself)
-
     def window_attention_core_supported(self, qkv, table_q, table_k, table_v):
         L, h, d, _ = table_q.shape
-        return (self.wa_core and self.wa_atomic_free and qkv.dim() == 2 and qkv.shape[1] == 3 * h * d and table_k.shape == table_q.shape == table_v.shape
+        return (self.wa_atomic_free and qkv.dim() == 2 and qkv.shape[1] == 3 * h * d and table_k.shape == table_q.shape == table_v.shape
                 and qkv.dtype == torch.float32 and qkv.is_contiguous() and self._wa_ok(d, L, qkv) and (h * d) % 4 == 0)
 
     def window_attention_core(self, qkv, index1, offsets, table_q, table_k, table_v, rel_idx, scale):
@@ -1298,10 +1292,10 @@ class HipBackend(CBackend):
         q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
         logits = torch.empty((m, h), dtype=torch.float32, device=qkv.device)
         self._call("wa_logits_forward_ordered", n, m, h, d, L, q, k, 3 * c, float(scale), offsets, index1, table_q, table_k, rel_idx, logits,
-                   self._wa_order(offsets))
+                   window_order_of(offsets))
         attn = self.segment_softmax(logits, offsets)
         out = torch.empty((n, c), dtype=torch.float32, device=qkv.device)
-        self._wa_rows(n, h, d, L, offsets, None, index1, rel_idx, attn, v, table_v, out, ldx=3 * c, order=self._wa_order(offsets))
+        self._wa_rows(n, h, d, L, offsets, None, index1, rel_idx, attn, v, table_v, out, ldx=3 * c, order=window_order_of(offsets))
         return out, attn
 
     def window_attention_core_backward(self, go, qkv, attn, index1, offsets, table_q, table_k, table_v, rel_idx, scale):
@@ -1313,10 +1307,10 @@ class HipBackend(CBackend):
         key_off, key_edge, key_q, key_rel = window_csc(index1, offsets, rel_idx, n_keys=n)
         gqkv = torch.empty_like(qkv)
         ga = torch.empty((m, h), dtype=torch.float32, device=qkv.device)
-        order = self._wa_order(offsets)   # (query side: window by window)
+        order = window_order_of(offsets)   # (query side: window by window)
         self._call("wa_grad_attn_ordered", n, m, h, d, L, go, c, offsets, index1, v, 3 * c, table_v, rel_idx, ga, order)
         attn_key = self._wa_permute(attn, key_edge)
-        korder = window_key_order(index1) if self.wa_window_order else None   # (key side: longest rows first, window by window)
+        korder = window_key_order(index1)   # (key side: longest rows first, window by window)
         self._wa_rows(n, h, d, 0, key_off, None, key_q, None, attn_key, go, None, gqkv[:, 2 * c:], ldo=3 * c, order=korder)          # grad_v
         gtv = self._wa_table_grad(n, h, d, L, offsets, None, rel_idx, attn, go, qkv)
         g = self.segment_softmax_backward(attn, ga, offsets)

@@ -28,7 +28,6 @@ EXTRA = {
     "window_edges.hip": ["-ffp-contract=off"],   # the quantised relative positions must round like the torch expression they replace
     "augment.hip": ["-ffp-contract=off"],        # the augmentation must round every product and sum as NumPy's elementwise loops do
     "openset_metrics.hip": ["-ffp-contract=off"],   # the average-precision terms are rounded as written (quotient, quotient, product, sum)
-    "window_attention.hip": ([f"-DPDF_WA_UE={os.environ['PDFOPS_WA_UE']}"] if os.environ.get("PDFOPS_WA_UE") else []),   # tuning knob (A/B builds)
 }
 
 

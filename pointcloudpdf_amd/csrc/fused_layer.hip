@@ -43,12 +43,6 @@ struct WaveLds {
     int ts, as;    // row strides of tile / qtile and of aux
 };
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Gather 32 channels [c0, c0+32) of the 64 rows listed in L.rowid into L.tile (coalesced: 8 lanes x 16 B per row).
 __device__ __forceinline__ void stage_rows(const WaveLds &L, const float *__restrict__ table, int C, int c0, int lane) {
     const int sub = lane >> 3, col = (lane & 7) * 4;

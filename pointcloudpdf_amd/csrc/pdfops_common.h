@@ -37,6 +37,14 @@ static inline int pdf_divup(long a, long b) { return (int)((a + b - 1) / b); }
 
 __device__ __forceinline__ int pdf_lane() { return (int)(threadIdx.x & 63); }
 
+// Hand-off between the lanes of ONE wave through LDS: what the lanes stored before it is visible to every lane's loads after it.
+// Every lane of the wave must reach it (wave-uniform control flow).
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // wave64 butterfly reductions (all lanes receive the result)
 __device__ __forceinline__ int pdf_wave_min_i32(int v) {
 #pragma unroll

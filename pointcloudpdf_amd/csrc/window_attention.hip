@@ -15,11 +15,17 @@
 //     atomics, fixed summation order (the reference's shared atomics are unordered);
 //   * true scatters (grad_k, grad_v: rows shared between queries) are fp32 atomics, one float per lane over whole rows;
 //   * table gradients collide massively (L ~ 50 rows receive millions of edges): see the per-head kernels further down (table
-//     slabs in LDS, gradients as one-hot MFMA products); the query-owned kernels here are the fallback for other shapes.
+//     slabs in LDS, gradients through LDS atomics); the query-owned kernels here are the fallback for other shapes.
 // d is any positive size (the reference throws unless d is 16 or 32); n_max is accepted for signature parity and unused.
 // All kernels: HBM / atomic-rate bound; algorithmic bytes are listed at the entry points.
+//
+// Two tiers of the backward live here, chosen by the `_l` entry points from the shape alone:
+//   per-head (`_h`)   d a power of two <= 64 and the head's slabs within 64 KB of LDS;
+//   generic           every other shape (head sizes that are no power of two, very long tables).
+// The d = 16, L <= 64 shape class of the model has a third, atomic-free and bit-reproducible backward of its own in
+// window_attention_bwd.hip (pdf_wa_*); HipBackend._wa_ok selects it, and the kernels of this file are then only the forward ops, the
+// segment softmax and the independent implementation the tests compare that backward against.
 #include "pdfops_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -227,7 +233,8 @@ __global__ __launch_bounds__(WB) void k_step2rv_bwd(int h, int d, const float *_
 // are staged in LDS once per workgroup, table gradients accumulate in LDS (ds_add_f32) and leave as one global atomic per
 // table element and workgroup, grad_q of the chunk accumulates in LDS and is stored plainly.  lane = (edge, channel) with the
 // channel fastest: key / value rows are read and scattered 4 * d contiguous bytes per edge.  Needs d a power of two <= 64 and
-// the slabs to fit 64 KB; anything else takes the generic kernels.
+// the slabs to fit 64 KB; anything else takes the generic kernels.  d = 16 comes through the same `d` argument as d = 32: the fast
+// path of that head size is window_attention_bwd.hip, not a specialisation here.
 constexpr int QCH = 64;   // queries per workgroup
 
 __device__ __forceinline__ int find_query(const int *__restrict__ offs, int nq, int m) {
@@ -379,408 +386,6 @@ __global__ __launch_bounds__(WB) void k_step2rv_bwd_h(int N, int h, int d, int L
 }
 
 
-// ---------------------------------------------------------------- table gradients on the matrix cores (d = 16)
-// grad_table[r, h, :, axis] = sum_m [rel_idx[m, axis] == r] * x[m, :] is a product of a one-hot (L x edges) matrix with the
-// (edges x 16) matrix of per-edge channel rows.  The k_*_h kernels pay three ds_add_f32 per (edge, channel) and table for it
-// (measured: they ARE the kernel time).  In the lane = (edge, channel) mapping a wave already holds 4 edges x 16 channels --
-// exactly the B operand of v_mfma_f32_16x16x4_f32 (B[k = lane/16][n = lane%16]); the A operand A[m = lane%16][k = lane/16] is
-// the one-hot test of the lane's OWN edge against row 16*rb + lane%16.  So every wave-trip issues 3 axes x ceil(L/16) MFMAs per
-// table and keeps G in accumulators (D[m = 4*(lane/16) + j][n = lane%16]); LDS atomics are needed once per wave at the end.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// Elements per lane and trip of the two kernels below (tuning knob, `PDFOPS_WA_UE=<n> python -m pointcloudpdf_amd.build`).  Measured on
-// the 2 x 80k-point ST-v1m1 step (A/B of round 3, profiles/r03_wa_ue_ab.txt): 2 -> 1.81 / 1.01 ms per launch (dot_prod backward /
-// step2 backward), 4 -> 2.34 / 1.10, 8 -> 2.24 / 1.08: more loads in flight per trip do not pay, the kernels are not waiting for their
-// gathers.
-#ifndef PDF_WA_UE
-#define PDF_WA_UE 2
-#endif
-constexpr int UE = PDF_WA_UE;
-
-template <int RB>
-__global__ __launch_bounds__(WB) void k_dot3_bwd_m16(int N, int h, int L, const float *__restrict__ go, const float *__restrict__ q,
-                                                     const int *__restrict__ offsets, const float *__restrict__ k,
-                                                     const int *__restrict__ index_k, const float *__restrict__ table_q,
-                                                     const float *__restrict__ table_k, const int *__restrict__ rel_idx,
-                                                     float *__restrict__ grad_q, float *__restrict__ grad_k,
-                                                     float *__restrict__ grad_table_q, float *__restrict__ grad_table_k) {
-    constexpr int d = 16;
-    extern __shared__ float sm[];
-    const int T = slab_floats(L, d);
-    float *tq = sm, *tk = tq + T, *gtq = tk + T, *gtk = gtq + T, *gqs = gtk + T;   // gqs: QCH * d
-    int *offs = reinterpret_cast<int *>(gqs + QCH * d);
-    const int hh = blockIdx.y, C = h * d;
-    const int q0 = blockIdx.x * QCH, nq = min(QCH, N - q0);
-    for (int j = threadIdx.x; j <= nq; j += WB) offs[j] = offsets[q0 + j];
-    stage_table(tq, table_q, L, C, d, hh);
-    stage_table(tk, table_k, L, C, d, hh);
-    for (int e = threadIdx.x; e < 2 * T + QCH * d; e += WB) gtq[e] = 0.f;
-    __syncthreads();
-    const int e0 = offs[0], e1 = offs[nq];
-    const long total = (long)(e1 - e0) * d;
-    const long padded = (total + 63) & ~63L;
-    const int lane = threadIdx.x & 63, i = lane & 15;
-    f32x4 aq[3][RB], ak[3][RB];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) { aq[a][rb] = (f32x4)(0.f); ak[a][rb] = (f32x4)(0.f); }
-    // Two elements per lane and trip, every load of a trip issued before the first use (index / scalar loads, then the rows that depend
-    // on them), no load under `if (live)` -- clamped edge id, effects masked (a load under a branch is a wait of its own); the
-    // query of an edge is found by stepping on from the lane's previous query (edges are in CSR order: 0-1 steps instead of a 6-step
-    // binary search through LDS).
-    int ql_hint = 0;
-    const int m_last = e1 > e0 ? e1 - 1 : e0;
-    for (long e = threadIdx.x; e < padded; e += UE * WB) {
-        bool live[UE]; int m[UE], ql[UE], r[UE][3], ik[UE]; float g[UE], xq[UE], xk[UE];
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const long eu = e + u * WB;
-            live[u] = eu < total;
-            m[u] = min(e0 + (int)(eu >> 4), m_last);
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            r[u][0] = rel_idx[(size_t)m[u] * 3]; r[u][1] = rel_idx[(size_t)m[u] * 3 + 1]; r[u][2] = rel_idx[(size_t)m[u] * 3 + 2];
-            g[u] = go[(size_t)m[u] * h + hh];
-            ik[u] = index_k[m[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            while (ql_hint + 1 < nq && offs[ql_hint + 1] <= m[u]) ++ql_hint;
-            ql[u] = ql_hint;
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            xq[u] = q[(size_t)(q0 + ql[u]) * C + hh * d + i];
-            xk[u] = k[(size_t)ik[u] * C + hh * d + i];
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const float gm = live[u] ? g[u] : 0.f;
-            // grad_q: the four edges a wave holds for channel i (lanes i, i + 16, i + 32, i + 48) are consecutive edges of the CSR list and
-            // mostly belong to ONE query: their contributions are added across the lanes first and one lane issues the LDS atomic (four
-            // same-address ds_add_f32 serialise); waves that straddle a query boundary take the per-lane path.
-            float cq = live[u] ? lds_table_sum(tq, r[u][0], r[u][1], r[u][2], d, i) * gm : 0.f;
-            const int ql0 = __shfl(ql[u], i, 64);
-            if (__ballot(ql[u] != ql0) == 0ull) {
-                cq += __shfl_xor(cq, 16, 64);
-                cq += __shfl_xor(cq, 32, 64);
-                if (lane < 16 && cq != 0.f) atomicAdd(&gqs[ql0 * d + i], cq);
-            } else if (live[u]) {
-                atomicAdd(&gqs[ql[u] * d + i], cq);
-            }
-            if (live[u]) pdf_atomic_add(grad_k + (size_t)ik[u] * C + hh * d + i, lds_table_sum(tk, r[u][0], r[u][1], r[u][2], d, i) * gm);
-            const float vq = xq[u] * gm, vk = xk[u] * gm;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb) {
-                    const float hot = (live[u] && r[u][a] == 16 * rb + i) ? 1.f : 0.f;
-                    aq[a][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(hot, vq, aq[a][rb], 0, 0, 0);
-                    ak[a][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(hot, vk, ak[a][rb], 0, 0, 0);
-                }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = 16 * rb + 4 * (lane >> 4) + j;
-                if (row < L) {
-                    atomicAdd(&gtq[row * slab_stride(d) + 3 * i + a], aq[a][rb][j]);
-                    atomicAdd(&gtk[row * slab_stride(d) + 3 * i + a], ak[a][rb][j]);
-                }
-            }
-    __syncthreads();
-    for (int e = threadIdx.x; e < nq * d; e += WB) grad_q[(size_t)(q0 + e / d) * C + hh * d + e % d] = gqs[e];
-    const int per = d * 3;
-    for (int e = threadIdx.x; e < L * per; e += WB) {
-        const int rr = e / per, x = e - rr * per;
-        const size_t dst = ((size_t)rr * C + (size_t)hh * d) * 3 + x;
-        const float a = gtq[rr * (per + 1) + x], b = gtk[rr * (per + 1) + x];
-        if (a != 0.f) pdf_atomic_add(grad_table_q + dst, a);
-        if (b != 0.f) pdf_atomic_add(grad_table_k + dst, b);
-    }
-}
-
-template <int RB>
-__global__ __launch_bounds__(WB) void k_step2rv_bwd_m16(int N, int h, int L, const float *__restrict__ go, const int *__restrict__ offsets,
-                                                        const int *__restrict__ index1, const float *__restrict__ attn,
-                                                        const float *__restrict__ v, const float *__restrict__ table,
-                                                        const int *__restrict__ rel_idx, float *__restrict__ grad_attn,
-                                                        float *__restrict__ grad_v, float *__restrict__ grad_table) {
-    constexpr int d = 16;
-    extern __shared__ float sm[];
-    const int T = slab_floats(L, d);
-    float *tb = sm, *gt = tb + T;
-    int *offs = reinterpret_cast<int *>(gt + T);
-    const int hh = blockIdx.y, C = h * d;
-    const int q0 = blockIdx.x * QCH, nq = min(QCH, N - q0);
-    for (int j = threadIdx.x; j <= nq; j += WB) offs[j] = offsets[q0 + j];
-    stage_table(tb, table, L, C, d, hh);
-    for (int e = threadIdx.x; e < T; e += WB) gt[e] = 0.f;
-    __syncthreads();
-    const int e0 = offs[0], e1 = offs[nq];
-    const long total = (long)(e1 - e0) * d;
-    const long padded = (total + 63) & ~63L;
-    const int lane = threadIdx.x & 63, i = lane & 15;
-    f32x4 acc[3][RB];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) acc[a][rb] = (f32x4)(0.f);
-    int ql_hint = 0;   // (trip structure as k_dot3_bwd_m16)
-    const int m_last = e1 > e0 ? e1 - 1 : e0;
-    for (long e = threadIdx.x; e < padded; e += UE * WB) {
-        bool live[UE]; int m[UE], ql[UE], r[UE][3], i1[UE]; float at[UE], gout[UE], vv[UE];
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const long eu = e + u * WB;
-            live[u] = eu < total;
-            m[u] = min(e0 + (int)(eu >> 4), m_last);
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            r[u][0] = rel_idx[(size_t)m[u] * 3]; r[u][1] = rel_idx[(size_t)m[u] * 3 + 1]; r[u][2] = rel_idx[(size_t)m[u] * 3 + 2];
-            at[u] = attn[(size_t)m[u] * h + hh];
-            i1[u] = index1[m[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            while (ql_hint + 1 < nq && offs[ql_hint + 1] <= m[u]) ++ql_hint;
-            ql[u] = ql_hint;
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            gout[u] = go[(size_t)(q0 + ql[u]) * C + hh * d + i];
-            vv[u] = v[(size_t)i1[u] * C + hh * d + i];
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const float x = live[u] ? at[u] * gout[u] : 0.f;
-            float part = (lds_table_sum(tb, r[u][0], r[u][1], r[u][2], d, i) + vv[u]) * gout[u];
-            if (live[u]) pdf_atomic_add(grad_v + (size_t)i1[u] * C + hh * d + i, x);
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb)
-                    acc[a][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32((live[u] && r[u][a] == 16 * rb + i) ? 1.f : 0.f, x, acc[a][rb], 0, 0, 0);
-            for (int o = 8; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-            if (live[u] && i == 0) grad_attn[(size_t)m[u] * h + hh] = part;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = 16 * rb + 4 * (lane >> 4) + j;
-                if (row < L) atomicAdd(&gt[row * slab_stride(d) + 3 * i + a], acc[a][rb][j]);
-            }
-    __syncthreads();
-    const int per = d * 3;
-    for (int e = threadIdx.x; e < L * per; e += WB) {
-        const int rr = e / per, x = e - rr * per;
-        const float a = gt[rr * (per + 1) + x];
-        if (a != 0.f) pdf_atomic_add(grad_table + ((size_t)rr * C + (size_t)hh * d) * 3 + x, a);
-    }
-}
-
-
-// ---------------------------------------------------------------- table gradients factored by query (d = 16, L <= 64)
-// Wherever the value that multiplies the one-hot row selector is constant over the edges of a query -- q[query(m)] for table_q of
-// dot_prod_with_idx_v3, grad_out[query(m)] for the table of attention_step2_with_rel_pos_value_v2 -- the table gradient factors:
-//     G[r, :, a] = sum_m [rel[m, a] = r] s_m x[query(m), :]  =  sum_q x[q, :] (x) S_q[a, r],      S_q[a, r] = sum_{m in q, rel[m, a] = r} s_m
-// i.e. a per-query HISTOGRAM of the edge scalars (three LDS adds per edge and head) followed by one small dense product per workgroup
-// (3 L x QF queries x 16 channels) instead of 3 ceil(L / 16) one-hot matrix-core products per FOUR edges (15/16 of whose rows multiply
-// zeros).  The same histogram gives the query-indexed result: grad_q[q, :] = sum_{a, r} S_q[a, r] table_q[r, :, a]; and for the value
-// table the per-edge term <grad_out[q, :], T(m, :)> becomes three lookups in the projection P_q[a, r] = <table[r, :, a], grad_out[q, :]>.
-// Only table_k of dot_prod_with_idx_v3 (value = the gathered key row, different per edge) keeps the one-hot products (k_dot3_bwd_k).
-constexpr int QF = 32;   // queries per workgroup of the factored kernels (histogram: QF x 3 L floats of LDS)
-
-// dot_prod_with_idx_v3 backward, query side: grad_q (written) and grad_table_q.  lane = edge for the histogram.
-__global__ __launch_bounds__(WB) void k_dot3_bwd_fq(int N, int h, int L, const float *__restrict__ go, const float *__restrict__ q,
-                                                    const int *__restrict__ offsets, const float *__restrict__ table_q,
-                                                    const int *__restrict__ rel_idx, float *__restrict__ grad_q, float *__restrict__ grad_table_q) {
-    constexpr int d = 16;
-    extern __shared__ float sm[];
-    const int T = slab_floats(L, d), W = 3 * L;
-    float *tq = sm, *qr = tq + T, *S = qr + QF * d;
-    int *offs = reinterpret_cast<int *>(S + QF * W);
-    const int hh = blockIdx.y, C = h * d;
-    const int q0 = blockIdx.x * QF, nq = min(QF, N - q0);
-    for (int j = threadIdx.x; j <= nq; j += WB) offs[j] = offsets[q0 + j];
-    stage_table(tq, table_q, L, C, d, hh);
-    for (int e = threadIdx.x; e < QF * d; e += WB) qr[e] = e < nq * d ? q[(size_t)(q0 + e / d) * C + hh * d + e % d] : 0.f;
-    for (int e = threadIdx.x; e < QF * W; e += WB) S[e] = 0.f;
-    __syncthreads();
-    const int e0 = offs[0], e1 = offs[nq];
-    for (int m = e0 + threadIdx.x; m < e1; m += WB) {
-        const int ql = find_query(offs, nq, m);
-        const float g = go[(size_t)m * h + hh];
-        const int r1 = rel_idx[(size_t)m * 3], r2 = rel_idx[(size_t)m * 3 + 1], r3 = rel_idx[(size_t)m * 3 + 2];
-        atomicAdd(&S[ql * W + r1], g);
-        atomicAdd(&S[ql * W + L + r2], g);
-        atomicAdd(&S[ql * W + 2 * L + r3], g);
-    }
-    __syncthreads();
-    const int st = slab_stride(d);
-    for (int e = threadIdx.x; e < nq * d; e += WB) {          // grad_q[q, i] = sum_{a, r} S_q[a, r] table_q[r, i, a]
-        const int ql = e / d, i = e % d;
-        const float *Sq = S + ql * W;
-        float acc = 0.f;
-        for (int r = 0; r < L; ++r)
-            acc += Sq[r] * tq[r * st + 3 * i] + Sq[L + r] * tq[r * st + 3 * i + 1] + Sq[2 * L + r] * tq[r * st + 3 * i + 2];
-        grad_q[(size_t)(q0 + ql) * C + hh * d + i] = acc;
-    }
-    for (int e = threadIdx.x; e < W * d; e += WB) {            // grad_table_q[r, i, a] += sum_q S_q[a, r] q[q, i]
-        const int x = e / d, i = e % d, a = x / L, r = x - a * L;
-        float acc = 0.f;
-        for (int ql = 0; ql < nq; ++ql) acc += S[ql * W + x] * qr[ql * d + i];
-        if (acc != 0.f) pdf_atomic_add(grad_table_q + ((size_t)r * C + (size_t)hh * d + i) * 3 + a, acc);
-    }
-}
-
-// dot_prod_with_idx_v3 backward, key side: grad_k (scatter) and grad_table_k -- the value row differs per edge, so the table gradient
-// stays a one-hot matrix-core product (see k_dot3_bwd_m16); one table per workgroup: 12 RB accumulator registers, one LDS slab that is
-// the table while the edges stream and the gradient slab afterwards.
-template <int RB>
-__global__ __launch_bounds__(WB) void k_dot3_bwd_k(int N, int h, int L, const float *__restrict__ go, const int *__restrict__ offsets,
-                                                   const float *__restrict__ k, const int *__restrict__ index_k,
-                                                   const float *__restrict__ table_k, const int *__restrict__ rel_idx,
-                                                   float *__restrict__ grad_k, float *__restrict__ grad_table_k) {
-    constexpr int d = 16;
-    extern __shared__ float sm[];
-    const int T = slab_floats(L, d);
-    float *tb = sm;
-    const int hh = blockIdx.y, C = h * d;
-    const int q0 = blockIdx.x * QCH, nq = min(QCH, N - q0);
-    stage_table(tb, table_k, L, C, d, hh);
-    __syncthreads();
-    const int e0 = offsets[q0], e1 = offsets[q0 + nq];
-    const long total = (long)(e1 - e0) * d;
-    const long padded = (total + 63) & ~63L;
-    const int lane = threadIdx.x & 63, i = lane & 15;
-    f32x4 acc[3][RB];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) acc[a][rb] = (f32x4)(0.f);
-    const int m_last = e1 > e0 ? e1 - 1 : e0;
-    for (long e = threadIdx.x; e < padded; e += UE * WB) {
-        bool live[UE]; int m[UE], r[UE][3], ik[UE]; float g[UE], x[UE];
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const long eu = e + u * WB;
-            live[u] = eu < total;
-            m[u] = min(e0 + (int)(eu >> 4), m_last);
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            r[u][0] = rel_idx[(size_t)m[u] * 3]; r[u][1] = rel_idx[(size_t)m[u] * 3 + 1]; r[u][2] = rel_idx[(size_t)m[u] * 3 + 2];
-            g[u] = go[(size_t)m[u] * h + hh];
-            ik[u] = index_k[m[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) x[u] = k[(size_t)ik[u] * C + hh * d + i];
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const float gm = live[u] ? g[u] : 0.f;
-            if (live[u]) pdf_atomic_add(grad_k + (size_t)ik[u] * C + hh * d + i, lds_table_sum(tb, r[u][0], r[u][1], r[u][2], d, i) * gm);
-            const float v = x[u] * gm;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb)
-                    acc[a][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32((live[u] && r[u][a] == 16 * rb + i) ? 1.f : 0.f, v, acc[a][rb], 0, 0, 0);
-        }
-    }
-    __syncthreads();                                    // every wave is done reading the table: the slab becomes the gradient slab
-    for (int e = threadIdx.x; e < T; e += WB) tb[e] = 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = 16 * rb + 4 * (lane >> 4) + j;
-                if (row < L) atomicAdd(&tb[row * slab_stride(d) + 3 * i + a], acc[a][rb][j]);
-            }
-    __syncthreads();
-    const int per = d * 3;
-    for (int e = threadIdx.x; e < L * per; e += WB) {
-        const int rr = e / per, xx = e - rr * per;
-        const float a = tb[rr * (per + 1) + xx];
-        if (a != 0.f) pdf_atomic_add(grad_table_k + ((size_t)rr * C + (size_t)hh * d) * 3 + xx, a);
-    }
-}
-
-// attention_step2_with_rel_pos_value_v2 backward, factored: grad_attn (written), grad_v (scatter), grad_table.
-__global__ __launch_bounds__(WB) void k_step2rv_bwd_f(int N, int h, int L, const float *__restrict__ go, const int *__restrict__ offsets,
-                                                      const int *__restrict__ index1, const float *__restrict__ attn,
-                                                      const float *__restrict__ v, const float *__restrict__ table,
-                                                      const int *__restrict__ rel_idx, float *__restrict__ grad_attn,
-                                                      float *__restrict__ grad_v, float *__restrict__ grad_table) {
-    constexpr int d = 16;
-    extern __shared__ float sm[];
-    const int T = slab_floats(L, d), W = 3 * L;
-    float *tb = sm, *gr = tb + T, *P = gr + QF * d, *S = P + QF * W;
-    int *offs = reinterpret_cast<int *>(S + QF * W);
-    const int hh = blockIdx.y, C = h * d;
-    const int q0 = blockIdx.x * QF, nq = min(QF, N - q0);
-    for (int j = threadIdx.x; j <= nq; j += WB) offs[j] = offsets[q0 + j];
-    stage_table(tb, table, L, C, d, hh);
-    for (int e = threadIdx.x; e < QF * d; e += WB) gr[e] = e < nq * d ? go[(size_t)(q0 + e / d) * C + hh * d + e % d] : 0.f;
-    for (int e = threadIdx.x; e < QF * W; e += WB) S[e] = 0.f;
-    __syncthreads();
-    const int st = slab_stride(d);
-    for (int e = threadIdx.x; e < nq * W; e += WB) {           // P_q[a, r] = <table[r, :, a], grad_out[q, :]>
-        const int ql = e / W, x = e - ql * W, a = x / L, r = x - a * L;
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < d; ++i) acc += tb[r * st + 3 * i + a] * gr[ql * d + i];
-        P[e] = acc;
-    }
-    __syncthreads();
-    const int e0 = offs[0], e1 = offs[nq];
-    for (int m = e0 + threadIdx.x; m < e1; m += WB) {          // lane = edge: grad_attn and the histogram of attn
-        const int ql = find_query(offs, nq, m);
-        const int r1 = rel_idx[(size_t)m * 3], r2 = rel_idx[(size_t)m * 3 + 1], r3 = rel_idx[(size_t)m * 3 + 2];
-        const float at = attn[(size_t)m * h + hh];
-        const float4 *vr = reinterpret_cast<const float4 *>(v + (size_t)index1[m] * C + hh * d);
-        const float *g = gr + ql * d;
-        float dot = 0.f;
-#pragma unroll
-        for (int c4 = 0; c4 < d / 4; ++c4) {
-            const float4 x = vr[c4];
-            dot += x.x * g[4 * c4] + x.y * g[4 * c4 + 1] + x.z * g[4 * c4 + 2] + x.w * g[4 * c4 + 3];
-        }
-        grad_attn[(size_t)m * h + hh] = dot + ((P[ql * W + r1] + P[ql * W + L + r2]) + P[ql * W + 2 * L + r3]);
-        atomicAdd(&S[ql * W + r1], at);
-        atomicAdd(&S[ql * W + L + r2], at);
-        atomicAdd(&S[ql * W + 2 * L + r3], at);
-    }
-    {                                                           // grad_v[index1[m], :] += attn[m] grad_out[q, :]: lane = (edge, channel)
-        const int i = threadIdx.x & 15;
-        int ql = 0;                                             // (a lane's edges ascend: the query is found by stepping on)
-        for (int m = e0 + (threadIdx.x >> 4); m < e1; m += WB / 16) {
-            while (offs[ql + 1] <= m) ++ql;
-            pdf_atomic_add(grad_v + (size_t)index1[m] * C + hh * d + i, attn[(size_t)m * h + hh] * gr[ql * d + i]);
-        }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < W * d; e += WB) {            // grad_table[r, i, a] += sum_q S_q[a, r] grad_out[q, i]
-        const int x = e / d, i = e % d, a = x / L, r = x - a * L;
-        float acc = 0.f;
-        for (int ql = 0; ql < nq; ++ql) acc += S[ql * W + x] * gr[ql * d + i];
-        if (acc != 0.f) pdf_atomic_add(grad_table + ((size_t)r * C + (size_t)hh * d + i) * 3 + a, acc);
-    }
-}
-
 // ---------------------------------------------------------------- segment softmax over the edges of a query
 // StratifiedTransformer normalises the attention logits per query and head with torch_scatter.scatter_softmax(src, index_0, dim=0)
 // (stratified_transformer_v1m1_origin.py:322-324; torch_scatter is an unvendored dependency, absent here): y[m,h] =
@@ -807,6 +412,7 @@ __global__ __launch_bounds__(WB) void k_seg_softmax_fwd(int N, int h, int HP, co
         float *b = buf + (threadIdx.x >> 6) * SM_CAP;
         const float *src = x + (size_t)s * h;
         for (int i = lane; i < cnt; i += 64) b[i] = src[i];
+        wave_sync();   // (a lane sweeps rows that other lanes staged)
         float *row = mine ? b + (size_t)(start - s) * h + hh : b;
         const int len = end - start;
         float mx = -3.0e38f;
@@ -815,6 +421,7 @@ __global__ __launch_bounds__(WB) void k_seg_softmax_fwd(int N, int h, int HP, co
         for (int m = 0; m < len; ++m) sum += __expf(row[m * h] - mx);
         const float inv = 1.f / sum;
         for (int m = 0; m < len; ++m) row[m * h] = __expf(row[m * h] - mx) * inv;
+        wave_sync();
         float *dst = y + (size_t)s * h;
         for (int i = lane; i < cnt; i += 64) dst[i] = b[i];
         return;
@@ -845,11 +452,13 @@ __global__ __launch_bounds__(WB) void k_seg_softmax_bwd(int N, int h, int HP, co
         float *by = buf + (threadIdx.x >> 6) * 2 * SM_CAP, *bg = by + SM_CAP;
         const float *sy = y + (size_t)s * h, *sg = gy + (size_t)s * h;
         for (int i = lane; i < cnt; i += 64) { by[i] = sy[i]; bg[i] = sg[i]; }
+        wave_sync();
         float *ry = mine ? by + (size_t)(start - s) * h + hh : by, *rg = mine ? bg + (size_t)(start - s) * h + hh : bg;
         const int len = end - start;
         float dot = 0.f;
         for (int m = 0; m < len; ++m) dot += ry[m * h] * rg[m * h];
         for (int m = 0; m < len; ++m) rg[m * h] = ry[m * h] * (rg[m * h] - dot);
+        wave_sync();
         float *dst = gx + (size_t)s * h;
         for (int i = lane; i < cnt; i += 64) dst[i] = bg[i];
         return;
@@ -947,31 +556,8 @@ extern "C" int pdf_dot_prod_with_idx_backward_v3_l(int N, int M, int h, int hdim
     if (M == 0 || !pow2_le64(hdim) || lds > 64 * 1024)
         return pdf_dot_prod_with_idx_backward_v3(N, M, h, hdim, 0, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, grad_q,
                                                  grad_k, grad_table_q, grad_table_k, stream);
-    const dim3 grid(pdf_divup(N, QCH), h);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hdim == 16 && L <= 64) {   // table gradients as one-hot MFMA products
-        // PDFOPS_WA_FACTORED=0: both tables as one-hot matrix-core products in one kernel (k_dot3_bwd_m16, rounds 1-3); default: the query
-        // side factored by query (k_dot3_bwd_fq), the key side as one-hot products of one table (k_dot3_bwd_k)
-        static const bool factored = [] { const char *v = getenv("PDFOPS_WA_FACTORED"); return !(v && v[0] == '0'); }();
-        const size_t lds_fq = sizeof(float) * (size_t)(L * (hdim * 3 + 1) + QF * hdim + QF * 3 * L) + sizeof(int) * (QF + 1);
-        const size_t lds_k = sizeof(float) * (size_t)(L * (hdim * 3 + 1));
-        if (factored)
-            k_dot3_bwd_fq<<<dim3(pdf_divup(N, QF), h), WB, lds_fq, st>>>(N, h, L, grad_out, q, index_q_offsets, table_q, rel_idx, grad_q, grad_table_q);
-#define PDF_DOT3_M16(RB_) do { if (factored) k_dot3_bwd_k<RB_><<<grid, WB, lds_k, st>>>(N, h, L, grad_out, index_q_offsets, k, index_k, table_k, rel_idx, \
-                                                                                      grad_k, grad_table_k); \
-        else k_dot3_bwd_m16<RB_><<<grid, WB, lds, st>>>(N, h, L, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, \
-                                                        grad_q, grad_k, grad_table_q, grad_table_k); } while (0)
-        switch ((L + 15) / 16) {
-            case 1: PDF_DOT3_M16(1); break;
-            case 2: PDF_DOT3_M16(2); break;
-            case 3: PDF_DOT3_M16(3); break;
-            default: PDF_DOT3_M16(4); break;
-        }
-#undef PDF_DOT3_M16
-        return pdf_launch_status();
-    }
-    k_dot3_bwd_h<<<grid, WB, lds, st>>>(N, h, hdim, L, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, grad_q, grad_k,
-                                        grad_table_q, grad_table_k);
+    k_dot3_bwd_h<<<dim3(pdf_divup(N, QCH), h), WB, lds, static_cast<hipStream_t>(stream)>>>(N, h, hdim, L, grad_out, q, index_q_offsets, k, index_k, table_q,
+                                                                                            table_k, rel_idx, grad_q, grad_k, grad_table_q, grad_table_k);
     return pdf_launch_status();
 }
 
@@ -1012,28 +598,8 @@ extern "C" int pdf_attention_step2_with_rel_pos_value_backward_v2_l(int N, int M
     if (!pow2_le64(hdim) || lds > 64 * 1024)
         return pdf_attention_step2_with_rel_pos_value_backward_v2(N, M, h, hdim, 0, grad_out, index0_offsets, index1, attn, v, table, rel_idx,
                                                                   grad_attn, grad_v, grad_table, stream);
-    const dim3 grid(pdf_divup(N, QCH), h);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hdim == 16 && L <= 64) {
-        static const bool factored = [] { const char *e = getenv("PDFOPS_WA_FACTORED"); return !(e && e[0] == '0'); }();
-        if (factored && !(((size_t)h * hdim) & 3) && !(reinterpret_cast<uintptr_t>(v) & 15)) {   // (float4 reads of the value rows)
-            const size_t lds_f = sizeof(float) * (size_t)(L * (hdim * 3 + 1) + QF * hdim + 2 * QF * 3 * L) + sizeof(int) * (QF + 1);
-            k_step2rv_bwd_f<<<dim3(pdf_divup(N, QF), h), WB, lds_f, st>>>(N, h, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx,
-                                                                         grad_attn, grad_v, grad_table);
-            return pdf_launch_status();
-        }
-#define PDF_S2_M16(RB_) k_step2rv_bwd_m16<RB_><<<grid, WB, lds, st>>>(N, h, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, \
-                                                                     grad_v, grad_table)
-        switch ((L + 15) / 16) {
-            case 1: PDF_S2_M16(1); break;
-            case 2: PDF_S2_M16(2); break;
-            case 3: PDF_S2_M16(3); break;
-            default: PDF_S2_M16(4); break;
-        }
-#undef PDF_S2_M16
-        return pdf_launch_status();
-    }
-    k_step2rv_bwd_h<<<grid, WB, lds, st>>>(N, h, hdim, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
+    k_step2rv_bwd_h<<<dim3(pdf_divup(N, QCH), h), WB, lds, static_cast<hipStream_t>(stream)>>>(N, h, hdim, L, grad_out, index0_offsets, index1, attn, v, table,
+                                                                                               rel_idx, grad_attn, grad_v, grad_table);
     return pdf_launch_status();
 }
 

@@ -202,6 +202,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2, 8))) void
             xw[e] = 4 * qd + e / CG < N ? xr[i] * xscale : 0.f;
         }
         store_entries();
+        wave_sync();   // (phase 1 reads entries that other lanes stored, and adds into rows that other lanes cleared)
         // everything the NEXT quad needs from global memory: in flight from here on
         const int qn = qd + nw, qnn = qn + nw;
         int off2 = 0;
@@ -214,6 +215,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2, 8))) void
         for (int wb = o0; wb < o4; wb += WIN) {
             if (wb != o0) {                       // a further window of a long quad: loaded in place (rare; the next quad's registers are in use,
                 const int we = min(o4, wb + WIN);  // so this one goes straight to LDS)
+                wave_sync();                       // (every lane is done with the window this one replaces)
                 for (int l = lane; l < we - wb; l += 64) {
                     const int e = wb + l;
                     rel_s[l * 3] = rel[(size_t)e * 3]; rel_s[l * 3 + 1] = rel[(size_t)e * 3 + 1]; rel_s[l * 3 + 2] = rel[(size_t)e * 3 + 2];
@@ -221,12 +223,14 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2, 8))) void
 #pragma unroll
                     for (int g = 0; g < HG; ++g) w_s[l * HG + g] = w[wi + g];
                 }
+                wave_sync();
             }
             if (p1) {
                 const int t1 = min(pe, wb + WIN);
                 int t = max(pb, wb);
                 // four entries at a time: their bins are read together and written back in order; the NEXT four entries' (bin, value)
-                // are read from the window before the write-back (the compiler keeps LDS accesses in program order)
+                // are read from the window before the write-back.  The row is this lane's alone: its read-modify-write needs program order
+                // within the lane only; what lanes hand to each other (window, cleared rows, finished rows) is ordered by the wave_sync()s
                 int b[4];
                 float v[4];
                 auto fetch = [&](int tt) {
@@ -248,6 +252,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2, 8))) void
                 for (; t < t1; ++t) prow[rel_s[(t - wb) * 3 + pa]] += w_s[(t - wb) * HG + pg];
             }
         }
+        wave_sync();   // (phase 2 reads the other lanes' histogram rows and owner rows)
         // phase 2: A[i = row][k = owner lk] from the histograms, B[k = owner lk][j = channel] from the owner rows
         float bv[HG];
 #pragma unroll
@@ -258,6 +263,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2, 8))) void
             for (int rb = 0; rb < 4; ++rb)
                 acc[t * 4 + rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(Sw[(lk * NP + t) * HS + rb * 16 + li], bv[t / 3], acc[t * 4 + rb], 0, 0, 0);
         off0 = off1; off1 = off2;
+        wave_sync();   // (the next quad's clear and stores overwrite what phase 2 read)
     }
     // the workgroup's slab: the four waves' accumulators added in wave order through LDS (element (tile, v, lane) at (4 tile + v) 64 + lane)
     __syncthreads();
@@ -300,12 +306,7 @@ __global__ __launch_bounds__(TB) void k_table_reduce(int G, int HGN, int HGsz, i
     grad_table[((size_t)r * h * D + (size_t)hg * CG + c) * 3 + a] = (s0 + s1) + (s2 + s3);
 }
 
-// ---------------------------------------------------------------------------------------------------------------- grad_attn
-// attention_step2_with_rel_pos_value_v2 backward, the edge-indexed result (relative_pos_encoding_cuda_kernel_v2.cu:441-470):
-//     grad_attn[m, hh] = < grad_out[q(m), hh, :], v[index1[m], hh, :] + T(m, hh, :) >
-// The table term factors through the projection P_q[a][r] = < table[r, hh, :, a], grad_out[q, hh, :] > (3 L dot products per query instead
-// of 3 x 16 multiply-adds per edge).  grid = (ceil(N / QF), h); lane = edge (value row: 4 x 16 bytes contiguous).
-constexpr int QF = 32;
+// ---------------------------------------------------------------------------------------------------------------- query chunks
 // The chunk's queries are positions q0 .. q0 + nq - 1 of `order` (null: the queries themselves): their edge ranges need not be adjacent,
 // so the lanes walk a VIRTUAL edge index over the chunk (pref: exclusive prefix of the row lengths, qst: first edge of every row).
 template <int QN>
@@ -325,41 +326,6 @@ __device__ __forceinline__ void chunk_rows(int *pref, int *qst, int *qid, const 
         if (jj == 0) pref[0] = 0;
     }
     __syncthreads();
-}
-
-__global__ __launch_bounds__(TB) void k_grad_attn(int N, int h, int L, const float *__restrict__ go, long ldg, const int *__restrict__ offsets,
-                                                  const int *__restrict__ index1, const float *__restrict__ v, long ldv, const float *__restrict__ table,
-                                                  const int *__restrict__ rel, float *__restrict__ grad_attn, const int *__restrict__ order) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *tb = sm, *gr = tb + 3 * L * D, *P = gr + QF * D;     // tb [3][L][16] | gr [QF][16] | P [QF][3 L]
-    int *offs = reinterpret_cast<int *>(P + QF * 3 * L), *qst = offs + QF + 1, *qid = qst + QF;
-    const int hh = blockIdx.y, q0 = blockIdx.x * QF, nq = min(QF, N - q0), W = 3 * L;
-    chunk_rows<QF>(offs, qst, qid, offsets, order, q0, nq);
-    stage_table<1>(tb, table, L, h, hh);
-    for (int e = threadIdx.x; e < QF * D; e += TB) gr[e] = e < nq * D ? go[(size_t)qid[e / D] * ldg + (size_t)hh * D + e % D] : 0.f;
-    __syncthreads();
-    for (int e = threadIdx.x; e < nq * W; e += TB) {
-        const int ql = e / W, x = e - ql * W;   // x = a * L + r
-        const float4 *t4 = reinterpret_cast<const float4 *>(tb + x * D), *g4 = reinterpret_cast<const float4 *>(gr + ql * D);
-        float acc = 0.f;
-#pragma unroll
-        for (int c4 = 0; c4 < D / 4; ++c4) { const float4 a = t4[c4], b = g4[c4]; acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-        P[e] = acc;
-    }
-    __syncthreads();
-    const int total = offs[nq];
-    int ql = 0;
-    for (int t = threadIdx.x; t < total; t += TB) {             // (a lane's virtual edges ascend: the query is found by stepping on)
-        while (offs[ql + 1] <= t) ++ql;
-        const int m = qst[ql] + (t - offs[ql]);
-        const int r1 = rel[(size_t)m * 3], r2 = rel[(size_t)m * 3 + 1], r3 = rel[(size_t)m * 3 + 2];
-        const float4 *vr = reinterpret_cast<const float4 *>(v + (size_t)index1[m] * ldv + (size_t)hh * D);
-        const float4 *g4 = reinterpret_cast<const float4 *>(gr + ql * D);
-        float dot = 0.f;
-#pragma unroll
-        for (int c4 = 0; c4 < D / 4; ++c4) { const float4 a = vr[c4], b = g4[c4]; dot += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-        grad_attn[(size_t)m * h + hh] = dot + ((P[ql * W + r1] + P[ql * W + L + r2]) + P[ql * W + 2 * L + r3]);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- fused logits
@@ -430,10 +396,10 @@ __global__ __launch_bounds__(TB) void k_permute_edges(long total, int h, const f
 
 static inline int head_group(int h) { return h % 3 == 0 ? 3 : 1; }
 static inline int table_head_group(int h) { return head_group(h); }
+constexpr int TABLE_WGS = 512;      // workgroups of k_table in flight over all head groups
 static inline int table_grid(int N, int h) {
     const int nchunks = (N + 15) / 16, hgn = h / table_head_group(h);      // (a workgroup = four waves = four owner quads at a time)
-    static const int target = [] { const char *e = getenv("PDFOPS_WA_TABLE_GRID"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-    int g = target / (hgn < 1 ? 1 : hgn);       // ~512 workgroups in flight over all head groups
+    int g = TABLE_WGS / (hgn < 1 ? 1 : hgn);
     if (g < 8) g = 8;
     if (g > nchunks) g = nchunks;
     return g < 1 ? 1 : g;
@@ -495,17 +461,9 @@ extern "C" int pdf_wa_grad_attn_ordered(int N, int M, int h, int d, int L, const
     if (N < 0 || M < 0 || h < 1 || d < 1 || L < 1 || !grad_out || !offsets || !index1 || !v || !table || !rel || !grad_attn) return PDF_ERR_BAD_ARG;
     if (N == 0 || M == 0) return PDF_OK;
     if (d != wb::D || L > wb::LMAX || (reinterpret_cast<uintptr_t>(v) & 15) || (ldv & 3) || ldv < (long)h * d || ldg < (long)h * d) return PDF_ERR_UNSUPPORTED;
-    static const bool factored = [] { const char *e = getenv("PDFOPS_WA_GRAD_ATTN"); return e && e[0] == 'f'; }();   // (A/B: the round-5 form)
-    if (!factored) {
-        if (reinterpret_cast<uintptr_t>(v) & 15) return PDF_ERR_UNSUPPORTED;
-        const size_t lds1 = sizeof(float) * (size_t)(3 * L * wb::D + wb::QL * wb::D) + sizeof(int) * (3 * wb::QL + 1);
-        wb::k_logits_fwd<false><<<dim3((unsigned)((N + wb::QL - 1) / wb::QL), (unsigned)h), wb::TB, lds1, static_cast<hipStream_t>(stream)>>>(
-            N, h, L, grad_out, ldg, v, ldv, 1.f, offsets, index1, table, nullptr, rel, grad_attn, order);
-        return pdf_launch_status();
-    }
-    const size_t lds = sizeof(float) * (size_t)(3 * L * wb::D + wb::QF * wb::D + wb::QF * 3 * L) + sizeof(int) * (3 * wb::QF + 1);
-    wb::k_grad_attn<<<dim3((unsigned)((N + wb::QF - 1) / wb::QF), (unsigned)h), wb::TB, lds, static_cast<hipStream_t>(stream)>>>(
-        N, h, L, grad_out, ldg, offsets, index1, v, ldv, table, rel, grad_attn, order);
+    const size_t lds = sizeof(float) * (size_t)(3 * L * wb::D + wb::QL * wb::D) + sizeof(int) * (3 * wb::QL + 1);
+    wb::k_logits_fwd<false><<<dim3((unsigned)((N + wb::QL - 1) / wb::QL), (unsigned)h), wb::TB, lds, static_cast<hipStream_t>(stream)>>>(
+        N, h, L, grad_out, ldg, v, ldv, 1.f, offsets, index1, table, nullptr, rel, grad_attn, order);
     return pdf_launch_status();
 }
 

@@ -34,8 +34,9 @@ def test_reference_wrapper_fixtures_on_gpu(p2, golden_dir, tag):
                                  (25, 700, 3, 16, 10, 50), (26, 900, 2, 16, 60, 80), (27, 400, 2, 32, 30, 70), (28, 300, 2, 16, 70, 40)])
 def test_hip_vs_oracle_bigger_graphs(p2, oracle_backend, cfg):
     """Edge lists longer than one workgroup pass (n_max 300 / 1000), 12 heads, a head size that is not a multiple of 4,
-    empty queries; d = 16 with L = 10 / 20 / 48 / 60 (1-4 one-hot MFMA row blocks), L = 70 and d = 32 (LDS-atomic kernels),
-    d = 8 / 20 (generic kernels).  Oracle side = the same wrappers with the CPU backend injected."""
+    empty queries.  The backward each case reaches: d = 16 with L = 10 / 20 / 48 / 60 (cases 21, 22, 25, 26) the atomic-free
+    kernels of csrc/window_attention_bwd.hip; L = 70, d = 32 and d = 8 (cases 28, 27, 23) the LDS-atomic `_h` kernels; d = 20
+    (case 24, no power of two) the generic kernels.  Oracle side = the same wrappers with the CPU backend injected."""
     from pointcloudpdf_amd import _native
 
     G = window_graph(*cfg)
@@ -53,9 +54,11 @@ def test_hip_vs_oracle_bigger_graphs(p2, oracle_backend, cfg):
                                  (35, 2600, 12, 16, 64, 70)])
 def test_atomic_free_backward_is_bit_reproducible_and_matches_the_atomic_kernels(p2, cfg):
     """csrc/window_attention_bwd.hip (round 5): grad_k / grad_v / the three table gradients as segmented sums over the edge list grouped
-    by key / by query instead of fp32 atomics.  Two evaluations are BIT-identical (fixed summation order), and every gradient equals the
-    atomic launchers of rounds 1-4 (PDFOPS_WA_ATOMICS=1) to rounding; 3 / 6 / 12 / 24 heads (groups of three heads per workgroup), 2
-    heads (single-head groups), one-row tables, queries without edges, keys nobody attends to."""
+    by key / by query instead of fp32 atomics.  Two evaluations are BIT-identical (fixed summation order), and every gradient equals an
+    independent implementation to rounding: with `wa_atomic_free = False` the same calls take the LDS-atomic `_h` kernels of
+    csrc/window_attention.hip (k_dot3_bwd_h, k_step2rv_bwd_h) and k_step1_bwd.  3 / 6 / 12 / 24 heads (groups of three heads per
+    workgroup), 2 heads (single-head groups), one-row tables, queries without edges, keys nobody attends to; n_max above 48 gives a quad
+    of owners more than one 192-entry window (the in-place window loads of wb::k_table)."""
     from pointcloudpdf_amd import _native
 
     be = _native.hip_backend()

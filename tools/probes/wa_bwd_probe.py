@@ -69,6 +69,7 @@ for level, layer in bb.layers_by_level().items():
         ("rows grad_k (CSC), length then window order", lambda: be._wa_rows(n, h, d, L, key_off, None, key_q, key_rel, g_key, q, tk, gqkv[:, c:2 * c], ldx=3 * c, xscale=0.25, ldo=3 * c, order=lorder)),
         ("rows grad_v (CSC), length then window order", lambda: be._wa_rows(n, h, d, 0, key_off, None, key_q, None, attn_key, go, None, gqkv[:, 2 * c:], ldo=3 * c, order=lorder)),
         ("table gtv (CSR)", lambda: be._wa_table_grad(n, h, d, L, offsets, None, rel, attn, go, qkv)),
+        ("softmax_fwd", lambda: be.segment_softmax(ga, offsets)),
         ("softmax_bwd", lambda: be.segment_softmax_backward(attn, ga, offsets)),
         ("rows grad_q (CSR, rows+table)", lambda: be._wa_rows(n, h, d, L, offsets, None, index1, rel, gsm, k, tq, gqkv[:, :c], ldx=3 * c, ldo=3 * c, oscale=0.25)),
         ("rows grad_k (CSC, rows+table)", lambda: be._wa_rows(n, h, d, L, key_off, None, key_q, key_rel, g_key, q, tk, gqkv[:, c:2 * c], ldx=3 * c, xscale=0.25, ldo=3 * c)),
@@ -78,7 +79,7 @@ for level, layer in bb.layers_by_level().items():
     print(f"level {level}: N={n} M={m} C={c} h={h} L={L} n_max={n_max} mean row {m / n:.1f}  blocks={layer.depth}")
     for name, fn in rows:
         us = t(fn)
-        if name not in ("logits_fwd", "rows fwd out (CSR, rows+table)") and "edge ids" not in name and "window order" not in name and "length" not in name:
+        if name not in ("logits_fwd", "softmax_fwd", "rows fwd out (CSR, rows+table)") and "edge ids" not in name and "window order" not in name and "length" not in name:
             total += us * layer.depth
         print(f"    {name:34s} {us:9.1f} us", flush=True)
 print(f"backward pieces x blocks per level: {total / 1e3:.2f} ms per step")
