@@ -44,8 +44,9 @@ extern "C" {
  * 8 = pdf_fragment_bounds / pdf_fragment_gather / pdf_fragment_vote added (no existing parameter list changed);
  * 9 = pdf_radius_neighbors_self_adaptive added (no existing parameter list changed);
  * 10 = pdf_lovasz_workspace_bytes / pdf_lovasz_forward / pdf_lovasz_backward added (no existing parameter list changed);
- * 11 = pdf_openset_metrics_workspace_bytes / pdf_openset_metrics added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 11
+ * 11 = pdf_openset_metrics_workspace_bytes / pdf_openset_metrics added (no existing parameter list changed);
+ * 12 = pdf_scene_bounds / pdf_window_keys_scene added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 12
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -677,6 +678,14 @@ int pdf_wa_grad_attn_ordered(int N, int M, int h, int d, int L, const float *gra
  * Same floating-point steps as torch.div(.., rounding_mode="floor" / "trunc") on float32 tensors: bit-identical keys. */
 int pdf_window_keys(int n, const float *xyz, const int *ends, int scenes, const float *lo, const float *hi, float window_size, int parity,
                     long long *kf, long long *kc, long long *wk, void *stream);
+/* The same with ONE ORIGIN PER SCENE (the precise tester: a fragment's partition must not depend on its batch mates).
+ *   pdf_scene_bounds      : lo, hi (scenes, 3) float32 = per-axis minimum / maximum of every scene's rows of xyz, one launch, exact
+ *   pdf_window_keys_scene : lo / hi (scenes, 3) -> every scene's keys are those of the scene collated alone through pdf_window_keys, plus the
+ *                           number of grid cells of the scenes in front of it: keys of two scenes never compare equal, and the edge tables
+ *                           built from them are, scene by scene, the tables of the scene alone (rows and key ids moved by the scene's start) */
+int pdf_scene_bounds(int n, const float *xyz, const int *ends, int scenes, float *lo, float *hi, void *stream);
+int pdf_window_keys_scene(int n, const float *xyz, const int *ends, int scenes, const float *lo, const float *hi, float window_size,
+                          int parity, long long *kf, long long *kc, long long *wk, void *stream);
 int pdf_window_edges_count(int n, const long long *kf_sorted, const long long *kf, int m, const long long *kcd_sorted, const long long *kc,
                            const long long *wk, const long long *wkd, int *count, int *seg, void *stream);
 int pdf_window_edges_fill(int n, const int *offsets, const int *seg, const int *order_f, const int *order_cd, const long long *wk,

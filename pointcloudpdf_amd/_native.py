@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 11   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 12   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -105,6 +105,8 @@ _HIP_ONLY_PROTOS = {
     "wa_logits_forward_ordered": "iiiiipplfppppppp",
     "wa_grad_attn_ordered": "iiiiiplppplpppp",
     "window_keys": "ippippfippp",
+    "window_keys_scene": "ippippfippp",
+    "scene_bounds": "ippipp",
     "window_edges_count": "ippipppppp",
     "window_edges_fill": "ipppppppffipppp",
     "group_forward": "iiiippppp",
@@ -1193,14 +1195,27 @@ class HipBackend(CBackend):
         self._wa_rows(n, h, d, L, offsets, None, index1, rel_idx, attn, v, table, out)
         return out
 
-    def window_keys(self, xyz, ends, lo, hi, window_size, parity):
+    def window_keys(self, xyz, ends, lo, hi, window_size, parity, per_scene=False):
         """(kf, kc, wk) int64 per point of one window partition (csrc/window_edges.hip we::k_keys; what stratified.window_keys composes from
-        ~45 torch ops): xyz (N, 3), ends (scenes) int32 scene ends, lo / hi (3) float32 = per-axis minimum / maximum of xyz."""
-        n = int(xyz.shape[0])
+        ~45 torch ops): xyz (N, 3), ends (scenes) int32 scene ends, lo / hi (3) float32 = per-axis minimum / maximum of xyz.
+        ``per_scene``: lo / hi (scenes, 3) (``scene_bounds``), every scene partitioned from its own origin (we::k_keys_scene; what
+        stratified.window_keys_scene composes)."""
+        n, scenes = int(xyz.shape[0]), int(ends.shape[0])
+        if tuple(lo.shape) != ((scenes, 3) if per_scene else (3,)) or lo.shape != hi.shape:
+            raise ValueError(f"window_keys: lo / hi of shape {tuple(lo.shape)} / {tuple(hi.shape)} for {scenes} scenes, per_scene={per_scene}")
         out = torch.empty((3, n), dtype=torch.int64, device=xyz.device)
-        self._call("window_keys", n, xyz.contiguous(), ends.int().contiguous(), int(ends.shape[0]), lo.float().contiguous(), hi.float().contiguous(),
-                   float(window_size), int(parity), out[0], out[1], out[2])
+        self._call("window_keys_scene" if per_scene else "window_keys", n, xyz.contiguous(), ends.int().contiguous(), scenes,
+                   lo.float().contiguous(), hi.float().contiguous(), float(window_size), int(parity), out[0], out[1], out[2])
         return out[0], out[1], out[2]
+
+    def scene_bounds(self, xyz, ends):
+        """(lo, hi) (scenes, 3) float32: per-axis minimum / maximum of every scene's rows of xyz (N, 3) float32 -- one launch, no host
+        read (csrc/window_edges.hip we::k_scene_bounds); ends (scenes) int32 ascending scene ends, the last one = N."""
+        _check(xyz, torch.float32, "xyz")
+        scenes = int(ends.shape[0])
+        out = torch.empty((2, scenes, 3), dtype=torch.float32, device=xyz.device)
+        self._call("scene_bounds", int(xyz.shape[0]), xyz.contiguous(), ends.int().contiguous(), scenes, out[0], out[1])
+        return out[0], out[1]
 
     def window_edges(self, xyz, kf, kc, wk, downsample_idx, c2w, qs, vmax):
         """The CSR-by-query edge table of one window partition (csrc/window_edges.hip; stratified_transformer_v1m1_origin.py:45-127 + the

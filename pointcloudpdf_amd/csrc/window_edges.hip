@@ -17,6 +17,8 @@
 // (WindowAttention.relative_position_index, :282-292) in the same pass.
 // Bit-identical to the reference's tables (tests/test_gpu_pointops2.py against oracle/window_tables.py, the restatement of :45-127).
 // Compiled with -ffp-contract=off: the quantisation below must round exactly like the torch expression it replaces.
+// The window keys come in two forms: one grid origin for the whole batch (we::k_keys, as upstream: training) and one origin per scene
+// (we::k_scene_bounds + we::k_keys_scene: the precise tester's batched fragments, every scene partitioned as if collated alone).
 #include "pdfops_common.h"
 
 namespace we {
@@ -154,6 +156,92 @@ __global__ void k_keys(int n, const float *__restrict__ xyz, const int *__restri
     wk[i] = (wc[0] << 42) | (wc[1] << 21) | wc[2];
 }
 
+// ---- per-scene origin: every scene of the batch is partitioned as if it were collated alone (the precise tester feeds one fragment per
+// forward upstream, engines/test.py:207-251; a batch of fragments must not couple their partitions through a shared minimum)
+#define WE_BOUNDS_THREADS 768   // a multiple of 3 and of 64: a thread keeps ONE axis over its whole walk of the scene's flat coordinates
+
+// one workgroup per scene: lo / hi (scenes, 3) = per-axis minimum / maximum of the scene's rows of xyz (exact: min / max do not depend
+// on the order).  An empty scene gets lo = hi = 0.
+__global__ __launch_bounds__(WE_BOUNDS_THREADS) void k_scene_bounds(int n, const float *__restrict__ xyz, const int *__restrict__ ends,
+                                                                      float *__restrict__ lo, float *__restrict__ hi) {
+    __shared__ float s_min[WE_BOUNDS_THREADS], s_max[WE_BOUNDS_THREADS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t f0 = 3 * (size_t)max(b ? ends[b - 1] : 0, 0), f1 = 3 * (size_t)min(max(ends[b], 0), n);   // (never past the n rows)
+    float mn = INFINITY, mx = -INFINITY;
+    for (size_t f = f0 + tid; f < f1; f += WE_BOUNDS_THREADS) {   // f0 and the stride are multiples of 3: axis = tid % 3 throughout
+        const float v = xyz[f];
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+    }
+    s_min[tid] = mn;
+    s_max[tid] = mx;
+    __syncthreads();
+    for (int s = WE_BOUNDS_THREADS / 2; s >= 3; s >>= 1) {        // 384 ... 3: every step keeps the axis (s is a multiple of 3)
+        if (tid < s) {
+            s_min[tid] = fminf(s_min[tid], s_min[tid + s]);
+            s_max[tid] = fmaxf(s_max[tid], s_max[tid + s]);
+        }
+        __syncthreads();
+    }
+    if (tid < 3) {
+        const bool empty = f1 <= f0;
+        lo[3 * b + tid] = empty ? 0.f : s_min[tid];
+        hi[3 * b + tid] = empty ? 0.f : s_max[tid];
+    }
+}
+
+// cells of one scene's grid: prod_d max(1, floor((hi_d [+ shift] - lo_d) / size) + 1) -- the stride voxel_grid gives the batch coordinate
+__device__ __forceinline__ i64 grid_cells(const float *__restrict__ lo, const float *__restrict__ hi, float size, float shift, int parity) {
+    i64 cells = 1;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float e = parity ? hi[d] + shift : hi[d];
+        i64 num = (i64)floor_div(e - lo[d], size) + 1;
+        if (num < 1) num = 1;
+        cells *= num;
+    }
+    return cells;
+}
+
+// k_keys with lo / hi (scenes, 3): point i of scene b gets the keys of b collated alone (scene index 0), moved up by the cells of the
+// scenes in front of it -- so the keys of two scenes never meet, and sorting by key keeps every scene's own order.
+__global__ void k_keys_scene(int n, const float *__restrict__ xyz, const int *__restrict__ ends, const float *__restrict__ lo,
+                             const float *__restrict__ hi, KeyArgs A, i64 *__restrict__ kf, i64 *__restrict__ kc, i64 *__restrict__ wk) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int b = 0;
+    while (b < A.scenes - 1 && i >= ends[b]) ++b;
+    const float *slo = lo + 3 * b, *shi = hi + 3 * b;
+    i64 key[2], wc[3];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const float size = g == 0 ? A.ws : 2.f * A.ws;
+        const float shift = A.parity ? 0.5f * size : 0.f;
+        i64 k = 0, stride = 1;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float p = A.parity ? xyz[3 * (size_t)i + d] + shift : xyz[3 * (size_t)i + d];
+            const float e = A.parity ? shi[d] + shift : shi[d];
+            const i64 cell = (i64)floor_div(p - slo[d], size);
+            i64 num = (i64)floor_div(e - slo[d], size) + 1;
+            if (num < 1) num = 1;
+            k += cell * stride;
+            stride *= num;
+        }
+        for (int t = 0; t < b; ++t) k += grid_cells(lo + 3 * t, hi + 3 * t, size, shift, A.parity);
+        key[g] = k;
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float r = xyz[3 * (size_t)i + d] - slo[d];
+        const float t = A.parity ? r + 0.5f * A.ws : r + 0.f;
+        wc[d] = (i64)truncf(t / A.ws);
+    }
+    kf[i] = key[0];
+    kc[i] = key[1];
+    wk[i] = (wc[0] << 42) | (wc[1] << 21) | wc[2];
+}
+
 }  // namespace we
 
 // Window keys of one Swin block's partition (parity 0: plain, 1: shifted by half a window).  xyz (n, 3); ends (scenes) int32 scene ends;
@@ -165,6 +253,28 @@ extern "C" int pdf_window_keys(int n, const float *xyz, const int *ends, int sce
     if (!xyz || !ends || scenes < 1 || !lo || !hi || !kf || !kc || !wk) return PDF_ERR_BAD_ARG;
     we::KeyArgs A{window_size, parity & 1, scenes};
     we::k_keys<<<pdf_divup(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n, xyz, ends, lo, hi, A, kf, kc, wk);
+    return pdf_launch_status();
+}
+
+// Per-axis minimum / maximum of every scene's coordinates in one launch.  xyz (n, 3); ends (scenes) int32 ascending scene ends, the
+// last one = n.  -> lo, hi (scenes, 3) float32 (an empty scene: zeros).
+extern "C" int pdf_scene_bounds(int n, const float *xyz, const int *ends, int scenes, float *lo, float *hi, void *stream) {
+    if (n < 0 || scenes < 0) return PDF_ERR_BAD_ARG;
+    if (scenes == 0) return PDF_OK;
+    if (!ends || !lo || !hi || (n > 0 && !xyz)) return PDF_ERR_BAD_ARG;
+    we::k_scene_bounds<<<scenes, WE_BOUNDS_THREADS, 0, static_cast<hipStream_t>(stream)>>>(n, xyz, ends, lo, hi);
+    return pdf_launch_status();
+}
+
+// pdf_window_keys with one origin per scene: lo / hi (scenes, 3) float32 (pdf_scene_bounds).  Every scene's keys are those of the scene
+// collated alone through pdf_window_keys plus the number of grid cells of the scenes in front of it (kf and kc each by their own grid).
+extern "C" int pdf_window_keys_scene(int n, const float *xyz, const int *ends, int scenes, const float *lo, const float *hi,
+                                     float window_size, int parity, long long *kf, long long *kc, long long *wk, void *stream) {
+    if (n < 0 || scenes < 0 || !(window_size > 0.f)) return PDF_ERR_BAD_ARG;
+    if (n == 0) return PDF_OK;
+    if (!xyz || !ends || scenes < 1 || !lo || !hi || !kf || !kc || !wk) return PDF_ERR_BAD_ARG;
+    we::KeyArgs A{window_size, parity & 1, scenes};
+    we::k_keys_scene<<<pdf_divup(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n, xyz, ends, lo, hi, A, kf, kc, wk);
     return pdf_launch_status();
 }
 

@@ -297,6 +297,45 @@ def window_keys(xyz, batch, window_size, xyz_min, parity):
     return kf, kc, (wc[:, 0] << 42) | (wc[:, 1] << 21) | wc[:, 2]
 
 
+def _grid_cells(lo, hi, size, shift):
+    """Cells of ``_voxel_grid``'s grid over one scene: prod_d max(1, floor((hi_d + shift - lo_d) / size_d) + 1) (int64 scalar tensor)."""
+    return (torch.div(hi + shift - lo, size, rounding_mode="floor").long() + 1).clamp_(min=1).prod()
+
+
+def scene_bounds(xyz, offset):
+    """(lo, hi) (scenes, 3): per-axis minimum / maximum of every scene's rows (an empty scene: zeros).  Device float32 tensors: one
+    launch of csrc/window_edges.hip, no host read; otherwise torch per scene."""
+    be = _native.backend_for(xyz) if xyz.is_cuda else None   # (host tensors: the composition needs no backend)
+    if hasattr(be, "scene_bounds") and xyz.dtype == torch.float32:
+        return be.scene_bounds(xyz, offset)
+    ends = [int(v) for v in offset.detach().cpu().tolist()]
+    rows = [torch.stack(torch.aminmax(xyz[a:z], dim=0)) if z > a else xyz.new_zeros(2, 3) for a, z in zip([0] + ends[:-1], ends)]
+    both = torch.stack(rows)
+    return both[:, 0].contiguous(), both[:, 1].contiguous()
+
+
+def window_keys_scene(xyz, offset, window_size, parity, bounds=None):
+    """``window_keys`` with ONE ORIGIN PER SCENE: every scene of the batch gets the keys it has when it is collated alone (batch index 0,
+    its own minimum / maximum), moved up by the number of grid cells of the scenes in front of it -- so keys of different scenes never
+    compare equal, sorting by key keeps every scene's own order, and the edge tables built from them are, scene by scene, the tables of
+    the scene alone.  This is what the reference's tester computes (one fragment per forward, engines/test.py:207-251, with
+    CenterShift(apply_z=False) moving every fragment's x/y minimum elsewhere).  The oracle of csrc/window_edges.hip we::k_keys_scene."""
+    ends = [int(v) for v in offset.detach().cpu().tolist()]
+    lo, hi = bounds if bounds is not None else scene_bounds(xyz, offset)
+    kf, kc, wk = [], [], []
+    base_f, base_c = xyz.new_zeros((), dtype=torch.long), xyz.new_zeros((), dtype=torch.long)
+    shift_f, shift_c = (0.5 * window_size, 0.5 * (2 * window_size)) if parity % 2 else (0.0, 0.0)
+    for s, (a, z) in enumerate(zip([0] + ends[:-1], ends)):
+        if z > a:
+            part = xyz[a:z]
+            f, c, w = window_keys(part, torch.zeros(z - a, dtype=torch.long, device=xyz.device), window_size, lo[s].to(xyz.dtype), parity)
+            kf.append(f + base_f); kc.append(c + base_c); wk.append(w)
+        base_f = base_f + _grid_cells(lo[s].to(xyz.dtype), hi[s].to(xyz.dtype), window_size, shift_f)
+        base_c = base_c + _grid_cells(lo[s].to(xyz.dtype), hi[s].to(xyz.dtype), 2 * window_size, shift_c)
+    empty = xyz.new_zeros(0, dtype=torch.long)
+    return tuple(torch.cat(v) if v else empty for v in (kf, kc, wk))
+
+
 class Mlp(nn.Module):
     """:130-153"""
 
@@ -357,7 +396,12 @@ class StratifiedGeometry:
     scene ends as Python ints, as the collate function has them) no call of the chain waits for the device."""
 
     def __init__(self, coord, offset, offset_host=None, downsample_scale=8, ratio=0.25, num_layers=4, stem_transformer=True, k=16, up_k=3,
-                 ball=None):
+                 ball=None, window_origin="batch"):
+        """``window_origin``: the ``origin`` of every level's ``BasicLayer.window_tables`` ("batch": as upstream, training; "scene": every
+        scene from its own minimum, the tester's batched fragments)."""
+        if window_origin not in ("batch", "scene"):
+            raise ValueError(f"StratifiedGeometry: window_origin={window_origin!r} (expected 'batch' or 'scene')")
+        self.window_origin = window_origin
         self.coord, self.offset = coord.contiguous(), offset.int()
         self.offset_host = [int(v) for v in (offset_host if offset_host is not None else offset.detach().cpu().tolist())]
         self.cfg = (downsample_scale, ratio, num_layers, stem_transformer)
@@ -420,7 +464,7 @@ class StratifiedGeometry:
                 else:
                     keys = self._sample(("keys", l), xyz, off, ends, lambda n: n // scale + 1)[0]
                 if layers is not None:
-                    self.windows[l] = layers[l].window_tables(xyz, off, keys)
+                    self.windows[l] = layers[l].window_tables(xyz, off, keys, origin=self.window_origin)
                 if l < num_layers - 1:
                     n_xyz = xyz[idx.long(), :].contiguous()
                     if layers is not None:
@@ -435,7 +479,7 @@ class StratifiedGeometry:
         (indices rebased to the batch's level arrays) and its own window tables.  Bit-identical to ``precompute`` per batch
         (tests/test_gpu_pointops2.py::test_stratified_group_prepass_is_the_per_batch_prepass)."""
         scale, ratio, num_layers, stem_transformer = geoms[0].cfg
-        assert stem_transformer and all(g.cfg == geoms[0].cfg for g in geoms)
+        assert stem_transformer and all(g.cfg == geoms[0].cfg and g.window_origin == geoms[0].window_origin for g in geoms)
         dev = geoms[0].coord.device
         to_dev = lambda v: torch.tensor(v, dtype=torch.int32).to(dev, non_blocking=True)
         nsc = [len(g.offset_host) for g in geoms]                       # scenes per batch
@@ -465,7 +509,7 @@ class StratifiedGeometry:
                         g.samples[("down", l)] = ((down[db:d_ends[z - 1]] - p0).contiguous(), to_dev([e - db for e in d_ends[a:z]]))
                     if layers is not None:
                         xb, ob = (g.coord if l == 0 else xyz[p0:ends[z - 1]]), (g.offset if l == 0 else to_dev(local_ends))
-                        g.windows[l] = layers[l].window_tables(xb, ob, g.samples[("keys", l)][0])
+                        g.windows[l] = layers[l].window_tables(xb, ob, g.samples[("keys", l)][0], origin=g.window_origin)
                         if l == 0:
                             g._ball()
                         if not last:
@@ -503,10 +547,10 @@ class StratifiedPrefetcher:
     host-side waits (partition sizes are data dependent) block that thread alone.  ``get()`` joins the worker, makes the consumer
     stream wait for the side stream and registers the tables with it."""
 
-    def __init__(self, model, windows=True):
+    def __init__(self, model, windows=True, window_origin="batch"):
         from concurrent.futures import ThreadPoolExecutor
 
-        self.model, self.windows = model, windows
+        self.model, self.windows, self.window_origin = model, windows, window_origin
         self.stream = torch.cuda.Stream()
         self.pool = ThreadPoolExecutor(max_workers=1)
         self.device = torch.cuda.current_device()
@@ -514,7 +558,7 @@ class StratifiedPrefetcher:
     def submit(self, batch):
         # the geometry's constructor may enqueue conversions (coord.contiguous(), offset.int() for the int64 offsets of collate_fn) on
         # the caller's stream: the event the side stream waits for is recorded AFTER them
-        geom = self.model.make_geometry(batch["coord"], batch["offset"], batch.get("offset_host"))
+        geom = self.model.make_geometry(batch["coord"], batch["offset"], batch.get("offset_host"), window_origin=self.window_origin)
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream())   # the batch's tensors were produced on the caller's stream
 
@@ -534,7 +578,7 @@ class StratifiedPrefetcher:
         ``ready``: the event engine.GroupedGeometryLoader recorded when the batches' tensors were handed over (on its copy stream when
         it moved them): the pre-pass waits for it AND for an event recorded here, after the conversions the geometry constructors may
         enqueue on the caller's stream."""
-        geoms = [self.model.make_geometry(b["coord"], b["offset"], b.get("offset_host")) for b in batches]
+        geoms = [self.model.make_geometry(b["coord"], b["offset"], b.get("offset_host"), window_origin=self.window_origin) for b in batches]
         handed_over = ready
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream())
@@ -642,20 +686,31 @@ class BasicLayer(nn.Module):
             for i in range(depth)])
         self.downsample = downsample(channel, out_channels, ratio, k) if downsample else None
 
-    def window_tables(self, xyz, offset, downsample_idx):
+    def window_tables(self, xyz, offset, downsample_idx, origin="batch"):
         """The edge tables of this layer's two window partitions (even blocks: plain, odd blocks: shifted by half a window) -- :468-536,
         which rebuilds them for every block although they depend on the coordinates and the block's parity only.  Per parity:
-        (index_0 sorted, index_1, CSR offsets of index_0, longest row, relative-position table rows of the first block's attention)."""
-        xyz_min, xyz_max = _colminmax(xyz)
+        (index_0 sorted, index_1, CSR offsets of index_0, longest row, relative-position table rows of the first block's attention).
+        ``origin``: "batch" -- the grid starts at the minimum over the whole collated batch, as upstream (a training batch); "scene" -- every
+        scene is partitioned from its own minimum, i.e. exactly as when it is collated alone (the tester's batched fragments)."""
+        if origin not in ("batch", "scene"):
+            raise ValueError(f"window_tables: origin={origin!r} (expected 'batch' or 'scene')")
+        per_scene = origin == "scene"
         be = _native.backend_for(xyz)
         on_device = hasattr(be, "window_keys") and xyz.dtype == torch.float32
-        if not on_device:
-            window_size = torch.tensor([self.window_size] * 3, dtype=xyz.dtype, device=xyz.device)
-            batch = offset2batch(offset, xyz.shape[0])
+        window_size = torch.tensor([self.window_size] * 3, dtype=xyz.dtype, device=xyz.device) if not on_device else None
+        if per_scene:   # (on the device: one launch, no host read -- csrc/window_edges.hip we::k_scene_bounds)
+            bounds = scene_bounds(xyz, offset)
+        else:
+            xyz_min, xyz_max = _colminmax(xyz)
+            if not on_device:
+                batch = offset2batch(offset, xyz.shape[0])
         tables, flags = {}, []
         for parity in range(2 if self.depth > 1 else 1):
-            if on_device:   # one launch (csrc/window_edges.hip we::k_keys): the same float32 steps as the torch composition below
-                kf, kc, wk = be.window_keys(xyz, offset, xyz_min, xyz_max, self.window_size, parity)
+            if on_device:   # one launch (csrc/window_edges.hip we::k_keys / k_keys_scene): the same float32 steps as the torch compositions
+                lo, hi = bounds if per_scene else (xyz_min, xyz_max)
+                kf, kc, wk = be.window_keys(xyz, offset, lo, hi, self.window_size, parity, per_scene=per_scene)
+            elif per_scene:
+                kf, kc, wk = window_keys_scene(xyz, offset, window_size, parity, bounds)
             else:
                 kf, kc, wk = window_keys(xyz, batch, window_size, xyz_min, parity)
             attn = self.blocks[parity].attn
@@ -794,10 +849,10 @@ class StratifiedTransformer(nn.Module):
     def layers_by_level(self):
         return {layer.level: layer for layer in self.layers}
 
-    def make_geometry(self, coord, offset, offset_host=None):
+    def make_geometry(self, coord, offset, offset_host=None, window_origin="batch"):
         """The batch's StratifiedGeometry (not yet computed): ``.precompute()`` it on any stream ahead of the step and pass it as
-        ``data_dict["st_geometry"]``."""
-        return StratifiedGeometry(coord, offset, offset_host, **self.geometry_cfg)
+        ``data_dict["st_geometry"]``.  ``window_origin="scene"``: the window partitions of a batch of test fragments (testing.SceneTester)."""
+        return StratifiedGeometry(coord, offset, offset_host, window_origin=window_origin, **self.geometry_cfg)
 
     def forward(self, data_dict):
         global _ACTIVE_GEOMETRY

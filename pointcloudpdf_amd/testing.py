@@ -7,7 +7,8 @@ device and folds one fragment per call with a single kernel (``pdf_vote_accumula
 derives from them: ``pred = votes.argmax(1)``, ``score = sum / count`` (0 where a point was never visited -- scatter_mean's
 convention).  ``fragment_inference`` is that loop, one fragment per forward.  The second half of the module is the tester proper:
 ``TestPipeline`` / ``SceneTester`` / ``OpenSegTester`` / ``IncrSegTester`` run a reference ``cfg.data.test`` dict on raw scenes with batched
-fragments, look-ahead geometry and an ordered, atomic-free batched vote (csrc/fragments.hip)."""
+fragments, look-ahead geometry (PT-v1's ``pdf_geometry``, or the StratifiedTransformer's ``st_geometry`` with one window origin per
+fragment) and an ordered, atomic-free batched vote (csrc/fragments.hip)."""
 import logging
 import os
 
@@ -61,7 +62,11 @@ def fragment_inference(segmentor, recognizer_score_fn, data, fragments, num_clas
 # group ahead (engine.GroupedGeometryLoader), votes folded per batch without atomics in the reference's summation order.
 #
 # Every norm on the path is BatchNorm in eval mode and every geometric op works per scene segment, so a batch of G fragments is G
-# independent forwards: the reference's ``fragment_batch_size = 1`` is a choice, not a requirement.
+# independent forwards: the reference's ``fragment_batch_size = 1`` is a choice, not a requirement.  For PT-v1 that holds as the model
+# stands.  The StratifiedTransformer's window partition starts at the minimum over the whole collated batch (right for a training batch),
+# and CenterShift(apply_z=False) moves every fragment's x/y minimum elsewhere: there the tester hands the model a geometry whose
+# partitions start at every fragment's OWN minimum (``st_backbone=``, StratifiedGeometry(window_origin="scene")), which makes the batch
+# G independent forwards again.
 #
 # Dtypes follow NumPy (>= 2) step by step: a float32 scene stays float32 through the shifts, ``coord *= scale`` multiplies in float64
 # and rounds back to the array's dtype, RandomRotateTargetAngle promotes to float64 (np.dot with the float64 matrix), and a fragment's
@@ -324,9 +329,16 @@ class SceneTester:
     bit-reproducible and bit-identical to feeding the fragments one at a time through ``FragmentVoter.add``."""
 
     def __init__(self, forward_fn, num_classes, pipeline, fragments_per_batch=4, group=None, prefetch_plan=None, with_segment=False,
-                 device=None):
-        """``group``: batches per look-ahead pre-pass; default 12, or as many as ``GroupedGeometryLoader.MAX_SCENES`` fragments allow."""
+                 device=None, st_backbone=None):
+        """``group``: batches per look-ahead pre-pass; default 12, or as many as ``GroupedGeometryLoader.MAX_SCENES`` fragments allow.
+        ``st_backbone``: the forward's ``stratified.StratifiedTransformer`` (anything with ``make_geometry`` / ``layers_by_level``): the
+        batches then carry ``batch["st_geometry"]`` instead -- FPS chain, neighbour tables and window partitions with one origin per
+        fragment -- from a ``StratifiedPrefetcher(st_backbone, window_origin="scene")`` one group ahead, or inline with ``group=0``."""
         from . import engine
+
+        if st_backbone is not None and not (hasattr(st_backbone, "make_geometry") and hasattr(st_backbone, "layers_by_level")):
+            raise TypeError("SceneTester: st_backbone must be a StratifiedTransformer (make_geometry / layers_by_level)")
+        self.st_backbone = st_backbone
 
         self.forward_fn, self.num_classes, self.pipeline = forward_fn, int(num_classes), pipeline
         self.fragments_per_batch = max(int(fragments_per_batch), 1)
@@ -339,17 +351,47 @@ class SceneTester:
         self.with_segment = with_segment
         self.device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.plan = dict(prefetch_plan or {})
-        self._loader = None
+        self._loader, self._prefetcher = None, None
+        if st_backbone is not None and self.group > 0 and not st_backbone.geometry_cfg.get("stem_transformer", True):
+            _LOG.info("SceneTester: StratifiedGeometry.precompute_group covers stem_transformer=True only: geometry inline (group=0)")
+            self.group = 0
+
+    def _st_inline(self, batches):
+        """The look-ahead's geometry, computed per batch on the consumer's stream (``group=0``, and every host-tensor run)."""
+        bb = self.st_backbone
+        for batch in batches:
+            geom = bb.make_geometry(batch["coord"], batch["offset"], batch.get("offset_host"), window_origin="scene")
+            yield dict(batch, st_geometry=geom.precompute(bb.layers_by_level()))
 
     def _loaded(self, batches):
+        if self.st_backbone is not None and (self.device.type != "cuda" or self.group == 0):
+            return self._st_inline(batches)
         if self.device.type != "cuda":
             return batches
         if self._loader is None:   # one loader (its side streams and their allocator pools) for every scene this tester sees
             from . import engine
 
-            self._loader = engine.GroupedGeometryLoader(None, group=self.group, **self.plan)
+            if self.st_backbone is not None:
+                from .stratified import StratifiedPrefetcher
+
+                self._prefetcher = StratifiedPrefetcher(self.st_backbone, window_origin="scene")
+                self._loader = engine.GroupedGeometryLoader(None, group=self.group, prefetcher=self._prefetcher, key="st_geometry")
+            else:
+                self._loader = engine.GroupedGeometryLoader(None, group=self.group, **self.plan)
         self._loader.loader = batches
         return self._loader
+
+    def close(self):
+        """Joins the look-ahead's worker thread and drops its side stream (also done when the tester is dropped)."""
+        pf, self._prefetcher, self._loader = self._prefetcher, None, None
+        if pf is not None:
+            pf.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (interpreter shutdown: the pool's module may be gone)
+            pass
 
     @torch.no_grad()
     def vote(self, st):
@@ -393,24 +435,34 @@ def _host_vote(logits, score, index, g, votes, ssum, scnt):
             scnt.index_add_(0, index[rows], torch.ones_like(score[rows]))
 
 
-_BATCH_KEYS = ("coord", "feat", "offset", "offset_host", "grid_coord", "pdf_geometry")
+_BATCH_KEYS = ("coord", "feat", "offset", "offset_host", "grid_coord", "pdf_geometry", "st_geometry")
 
 
 def _cfg_get(cfg, key, default=None):
     return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
 
 
+def _st_backbone(model):
+    """The segmentor's backbone when it is a StratifiedTransformer (it builds its own geometry: ``make_geometry``), else None."""
+    bb = getattr(model, "backbone", None)
+    return bb if bb is not None and hasattr(bb, "make_geometry") else None
+
+
 class _TesterBase:
     """What the two testers share: the scene loop, the result files and the class histograms (test.py:189-266, 572-634)."""
 
-    def __init__(self, cfg, num_classes, forward_fn, with_segment):
+    def __init__(self, cfg, num_classes, forward_fn, with_segment, st_backbone=None):
         data = _cfg_get(cfg, "data")
         self.cfg = cfg
         self.ignore_index = int(_cfg_get(data, "ignore_index", -1))
         self.dim_pred = int(num_classes)
         self.pipeline = TestPipeline(_cfg_get(data, "test"))
         opts = {k: _cfg_get(cfg, k) for k in ("fragments_per_batch", "group", "prefetch_plan") if _cfg_get(cfg, k) is not None}
-        self.scene_tester = SceneTester(forward_fn, self.dim_pred, self.pipeline, with_segment=with_segment, device=_cfg_get(cfg, "device"), **opts)
+        self.scene_tester = SceneTester(forward_fn, self.dim_pred, self.pipeline, with_segment=with_segment, device=_cfg_get(cfg, "device"),
+                                        st_backbone=st_backbone, **opts)
+
+    def close(self):
+        self.scene_tester.close()
 
     def _labels(self, st):
         return st["segment"]
@@ -503,7 +555,7 @@ class OpenSegTester(_TesterBase):
             return logits, score.reshape(-1)
 
         data = _cfg_get(cfg, "data")
-        super().__init__(cfg, int(_cfg_get(data, "num_classes")), forward, with_segment=not is_msp)
+        super().__init__(cfg, int(_cfg_get(data, "num_classes")), forward, with_segment=not is_msp, st_backbone=_st_backbone(model))
         self.unknown_label = [int(v) for v in _cfg_get(cfg, "unknown_label", [])]
         self.mask_known = np.ones(self.dim_pred, dtype=bool)
         self.mask_known[self.unknown_label] = False
@@ -569,6 +621,9 @@ class IncrSegTester(_TesterBase):
 
     def __init__(self, step, cfg):
         learner = getattr(step, "learner", step)
+        if isinstance(learner, torch.nn.Module) and any(hasattr(m, "make_geometry") for m in learner.modules()):
+            raise NotImplementedError("IncrSegTester: a StratifiedTransformer learner -- the incremental stage is PointTransformer-V1 only "
+                                      "(the reference has no ST incremental recipe); use OpenSegTester for ST-v1m1")
         learner.eval()
 
         def forward(batch):
