@@ -5,11 +5,9 @@
 //   k_lv_keys     lane = row: softmax in registers -> prob; per (class, row) the sort key ~bits(e), e = |fg - p| (a non-negative float:
 //                 its bit pattern is monotone as an unsigned integer, the complement sorts descending; ignored rows get the last key
 //                 0xFFFFFFFF) and the payload row | fg << 31, both class-major (C segments of N).
-//   4 x (k_lv_hist, k_lv_scan, k_lv_scatter)
-//                 batched stable LSD radix sort, 8-bit digits, class = grid.y, tiles of 2048 keys.  Histogram per (class, digit, tile),
-//                 exclusive scan over (digit, tile), scatter with the rank inside the tile formed from wave ballots (lanes with an equal
-//                 digit, lower lane first) + per-wave digit counters: equal keys keep ascending row order.  Ping-pong between two buffers.
-//   k_lv_fgcount, k_lv_fgscan
+//   4 x (k_ts_hist, k_ts_scan_segments, k_ts_scatter)
+//                 the batched stable radix sort of csrc/tile_sort.h, segment = class, one-level scan: equal keys keep ascending row order.
+//   k_lv_fgcount, k_ts_scan_short
 //                 foreground count of every tile of the sorted order, its exclusive scan and the class totals G.
 //   k_lv_grad     F_i = inclusive foreground count, I = G - F_i, U = G + (i + 1) - F_i.  J_i - J_{i-1} from the integer counts in double
 //                 without a difference of two nearly equal quotients: 1 / U on a foreground element, I / (U (U - 1)) on a background
@@ -23,19 +21,14 @@
 // An element with key 0xFFFFFFFF is an ignored row or has e == 0: it contributes nothing either way, so the two may share the key
 // (ignored rows are background, and every element with e > 0 sorts before them: no count that matters sees them).
 // Bound: HBM (the sort moves 16 NC bytes per pass, four passes).
-#include "pdfops_common.h"
+#include "tile_sort.h"
 
 namespace {
 
-constexpr int LB = 256;
-constexpr int ITEMS = 8;                 // keys per lane and tile: wave w owns 512 consecutive keys, round r the 64 at w * 512 + r * 64
-constexpr int TILE = LB * ITEMS;         // 2048
-constexpr int WAVES = LB / 64;
-constexpr int RADIX = 256;               // 8-bit digits, four passes
+using namespace tile_sort;   // LB, ITEMS, TILE, WAVES, RADIX, pos: the sort's tile geometry is this pass's too
+
 constexpr int MAXC = 64;
 constexpr unsigned LAST_KEY = 0xFFFFFFFFu;
-
-__device__ __forceinline__ size_t lv_pos(int tile, int w, int r, int lane) { return (size_t)tile * TILE + w * (ITEMS * 64) + r * 64 + lane; }
 
 template <int W>
 __global__ __launch_bounds__(LB) void k_lv_keys(long n, int c, const float *__restrict__ logits, const long *__restrict__ target, long ignore,
@@ -76,97 +69,6 @@ __global__ __launch_bounds__(LB) void k_lv_keys(long n, int c, const float *__re
     if (threadIdx.x == 0) bad[blockIdx.x] = (unsigned)anybad;
 }
 
-// hist[(cls * 256 + digit) * ntiles + tile] = number of keys of the tile with that digit (integer LDS counters: the result does not depend
-// on the order of arrival)
-__global__ __launch_bounds__(LB) void k_lv_hist(long n, int ntiles, int shift, const unsigned *__restrict__ keys, unsigned *__restrict__ hist) {
-    __shared__ unsigned h[RADIX];
-    const int tile = blockIdx.x, cls = blockIdx.y;
-    h[threadIdx.x] = 0u;
-    __syncthreads();
-    const unsigned *k = keys + (size_t)cls * n;
-    for (int i = 0; i < ITEMS; ++i) {
-        const size_t p = (size_t)tile * TILE + i * LB + threadIdx.x;
-        if (p < (size_t)n) atomicAdd(&h[(k[p] >> shift) & (RADIX - 1)], 1u);
-    }
-    __syncthreads();
-    hist[((size_t)cls * RADIX + threadIdx.x) * ntiles + tile] = h[threadIdx.x];
-}
-
-// exclusive scan of the workgroup's 256 values (lane order); `s` = 256 words of LDS, free on entry, free again after the call
-__device__ __forceinline__ unsigned lv_block_excl_scan(unsigned v, unsigned *s) {
-    unsigned x = v;
-    s[threadIdx.x] = x;
-    __syncthreads();
-    for (int o = 1; o < LB; o <<= 1) {
-        const unsigned y = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0u;
-        __syncthreads();
-        x += y;
-        s[threadIdx.x] = x;
-        __syncthreads();
-    }
-    return x - v;
-}
-
-// in place: hist[cls][digit][tile] -> number of keys of the class that precede the (digit, tile) group in the pass's output.
-// One workgroup per class, lane = digit.
-__global__ __launch_bounds__(LB) void k_lv_scan(int ntiles, unsigned *__restrict__ hist) {
-    __shared__ unsigned s[LB];
-    unsigned *h = hist + ((size_t)blockIdx.x * RADIX + threadIdx.x) * ntiles;
-    unsigned sum = 0u;
-    for (int t = 0; t < ntiles; ++t) sum += h[t];
-    unsigned run = lv_block_excl_scan(sum, s);
-    for (int t = 0; t < ntiles; ++t) { const unsigned v = h[t]; h[t] = run; run += v; }
-}
-
-// stable scatter of one tile: position = start of the (digit, tile) group + keys of that digit in the tile's earlier waves + in the wave's
-// earlier rounds + among the round's lower lanes.
-__global__ __launch_bounds__(LB) void k_lv_scatter(long n, int ntiles, int shift, const unsigned *__restrict__ keys_in,
-                                                   const unsigned *__restrict__ vals_in, const unsigned *__restrict__ hist,
-                                                   unsigned *__restrict__ keys_out, unsigned *__restrict__ vals_out) {
-    __shared__ unsigned cnt[WAVES][RADIX];
-    const int tile = blockIdx.x, cls = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const size_t seg = (size_t)cls * n;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) cnt[i][threadIdx.x] = 0u;
-    __syncthreads();
-    unsigned key[ITEMS], val[ITEMS], off[ITEMS];
-    const unsigned long long lower = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < ITEMS; ++r) {
-        const size_t p = lv_pos(tile, w, r, lane);
-        const bool valid = p < (size_t)n;
-        key[r] = valid ? keys_in[seg + p] : 0u;
-        val[r] = valid ? vals_in[seg + p] : 0u;
-        const unsigned d = (key[r] >> shift) & (RADIX - 1);
-        unsigned long long peers = __ballot(valid);   // lanes of the round with this lane's digit
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const unsigned before = valid ? cnt[w][d] : 0u;   // the wave's own counters: no other wave touches them
-        off[r] = before + (unsigned)__popcll(peers & lower);
-        __syncthreads();
-        if (valid && (peers & lower) == 0ull) cnt[w][d] = before + (unsigned)__popcll(peers);   // the group's lowest lane
-        __syncthreads();
-    }
-    {   // lane = digit: the waves' counts become the waves' starting positions
-        unsigned run = hist[((size_t)cls * RADIX + threadIdx.x) * ntiles + tile];
-#pragma unroll
-        for (int i = 0; i < WAVES; ++i) { const unsigned v = cnt[i][threadIdx.x]; cnt[i][threadIdx.x] = run; run += v; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ITEMS; ++r) {
-        if (lv_pos(tile, w, r, lane) < (size_t)n) {
-            const unsigned q = cnt[w][(key[r] >> shift) & (RADIX - 1)] + off[r];   // < n: the groups partition the class's n keys
-            keys_out[seg + q] = key[r];
-            vals_out[seg + q] = val[r];
-        }
-    }
-}
-
 // fgcnt[cls * ntiles + tile] = foreground elements among the tile's sorted positions
 __global__ __launch_bounds__(LB) void k_lv_fgcount(long n, int ntiles, const unsigned *__restrict__ vals, unsigned *__restrict__ fgcnt) {
     __shared__ unsigned red[WAVES];
@@ -184,18 +86,6 @@ __global__ __launch_bounds__(LB) void k_lv_fgcount(long n, int ntiles, const uns
         for (int i = 0; i < WAVES; ++i) a += red[i];
         fgcnt[(size_t)cls * ntiles + tile] = a;
     }
-}
-
-// in place: fgcnt[cls][tile] -> foreground elements before the tile; total[cls] = G.  One workgroup per class.
-__global__ __launch_bounds__(LB) void k_lv_fgscan(int ntiles, unsigned *__restrict__ fgcnt, unsigned *__restrict__ total) {
-    __shared__ unsigned s[LB];
-    unsigned *f = fgcnt + (size_t)blockIdx.x * ntiles;
-    const int per = (ntiles + LB - 1) / LB, t0 = min(ntiles, (int)threadIdx.x * per), t1 = min(ntiles, t0 + per);
-    unsigned sum = 0u;
-    for (int t = t0; t < t1; ++t) sum += f[t];
-    unsigned run = lv_block_excl_scan(sum, s);
-    for (int t = t0; t < t1; ++t) { const unsigned v = f[t]; f[t] = run; run += v; }
-    if (threadIdx.x == LB - 1) total[blockIdx.x] = run;
 }
 
 // a class is averaged when it occurs among the kept rows and the caller's mask (class_seen) admits it
@@ -217,7 +107,7 @@ __global__ __launch_bounds__(LB) void k_lv_grad(long n, int c, int ntiles, const
     unsigned mine = 0u;
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
-        const size_t p = lv_pos(tile, w, r, lane);
+        const size_t p = pos(tile, w, r, lane);
         const bool valid = p < (size_t)n;
         key[r] = valid ? keys[seg + p] : LAST_KEY;
         val[r] = valid ? vals[seg + p] : 0u;
@@ -233,7 +123,7 @@ __global__ __launch_bounds__(LB) void k_lv_grad(long n, int c, int ntiles, const
     double acc = 0.0;
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
-        const size_t p = lv_pos(tile, w, r, lane);
+        const size_t p = pos(tile, w, r, lane);
         const bool fg = val[r] >> 31;
         const double f = (double)(run + (unsigned)__popcll(fgm[r] & upto));
         run += (unsigned)__popcll(fgm[r]);
@@ -311,8 +201,6 @@ __global__ __launch_bounds__(LB) void k_lv_bwd(long total, const float *__restri
     for (long e = (long)blockIdx.x * LB + threadIdx.x; e < total; e += (long)gridDim.x * LB) out[e] = dlogits[e] * s;
 }
 
-inline size_t lv_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct LvWorkspace {
     unsigned *keys[2], *vals[2], *hist, *fgcnt, *total, *bad;
     double *part;
@@ -322,16 +210,15 @@ struct LvWorkspace {
 LvWorkspace lv_carve(char *base, long n, int c) {
     const size_t nt = (size_t)((n + TILE - 1) / TILE), nc = (size_t)n * c;
     LvWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t b) { char *p = reinterpret_cast<char *>(reinterpret_cast<uintptr_t>(base) + o); o += lv_align(b); return p; };
-    w.part = reinterpret_cast<double *>(take(nt * c * sizeof(double)));
-    for (int i = 0; i < 2; ++i) w.keys[i] = reinterpret_cast<unsigned *>(take(nc * 4));
-    for (int i = 0; i < 2; ++i) w.vals[i] = reinterpret_cast<unsigned *>(take(nc * 4));
-    w.hist = reinterpret_cast<unsigned *>(take(nt * c * RADIX * 4));
-    w.fgcnt = reinterpret_cast<unsigned *>(take(nt * c * 4));
-    w.total = reinterpret_cast<unsigned *>(take((size_t)MAXC * 4));
-    w.bad = reinterpret_cast<unsigned *>(take(nt * 4));
-    w.bytes = o;
+    PdfCarver ws{base};
+    w.part = ws.take<double>(nt * c);
+    for (int i = 0; i < 2; ++i) w.keys[i] = ws.take<unsigned>(nc);
+    for (int i = 0; i < 2; ++i) w.vals[i] = ws.take<unsigned>(nc);
+    w.hist = ws.take<unsigned>(nt * c * RADIX);
+    w.fgcnt = ws.take<unsigned>(nt * c);
+    w.total = ws.take<unsigned>((size_t)MAXC);
+    w.bad = ws.take<unsigned>(nt);
+    w.bytes = ws.off;
     return w;
 }
 
@@ -356,14 +243,9 @@ extern "C" int pdf_lovasz_forward(long n, int c, const float *logits, const long
     if (c <= 16) k_lv_keys<16><<<(unsigned)nt, LB, 0, s>>>(n, c, logits, target, ignore, prob, w.keys[0], w.vals[0], w.bad);
     else if (c <= 32) k_lv_keys<32><<<(unsigned)nt, LB, 0, s>>>(n, c, logits, target, ignore, prob, w.keys[0], w.vals[0], w.bad);
     else k_lv_keys<MAXC><<<(unsigned)nt, LB, 0, s>>>(n, c, logits, target, ignore, prob, w.keys[0], w.vals[0], w.bad);
-    int cur = 0;
-    for (int shift = 0; shift < 32; shift += 8, cur ^= 1) {   // four passes, whatever the data: nothing is decided on the host
-        k_lv_hist<<<grid, LB, 0, s>>>(n, nt, shift, w.keys[cur], w.hist);
-        k_lv_scan<<<(unsigned)c, LB, 0, s>>>(nt, w.hist);
-        k_lv_scatter<<<grid, LB, 0, s>>>(n, nt, shift, w.keys[cur], w.vals[cur], w.hist, w.keys[cur ^ 1], w.vals[cur ^ 1]);
-    }
+    const int cur = sort<unsigned, false>(n, c, w.keys, w.vals, w.hist, nullptr, s);
     k_lv_fgcount<<<grid, LB, 0, s>>>(n, nt, w.vals[cur], w.fgcnt);
-    k_lv_fgscan<<<(unsigned)c, LB, 0, s>>>(nt, w.fgcnt, w.total);
+    k_ts_scan_short<<<(unsigned)c, LB, 0, s>>>(nt, w.fgcnt, w.total);   // -> foreground before the tile; total[cls] = G
     k_lv_grad<<<grid, LB, 0, s>>>(n, c, nt, w.keys[cur], w.vals[cur], w.fgcnt, w.total, class_mask, dlogits, w.part);
     k_lv_loss<<<1, LB, 0, s>>>(c, nt, w.part, w.total, class_mask, w.bad, loss);
     long g = (n + LB - 1) / LB;

@@ -11,13 +11,11 @@
 //                 every valid row (the only score with that key is one NaN pattern, and a NaN on a valid row makes both areas NaN anyway).
 //   k_om_sums     one workgroup per class adds the partial rows: hist = intersection | output + target - intersection | target (int64);
 //                 one more workgroup the three counts -> totals.
-//   4 x (k_om_hist, k_om_scan_chunks, k_om_scan_totals, k_om_scatter)
-//                 stable LSD radix sort, 8-bit digits, tiles of 2048 keys (every pass of an LSD sort has to be stable; rank inside the
-//                 tile from wave ballots + per-wave digit counters as csrc/lovasz.hip).  ONE segment of up to 2^31 - 2 keys, so the
-//                 exclusive scan over the (digit, tile) counts -- a linear array of 256 * tiles words -- is two-level: chunks of 1024
-//                 words are scanned by a workgroup each, the chunk totals by one workgroup, and the consumer adds chunk prefix + own value.
+//   4 x (k_ts_hist, k_ts_scan_chunks, k_ts_scan_short, k_ts_scatter)
+//                 the stable radix sort of csrc/tile_sort.h: ONE segment of up to 2^31 - 2 keys, so with its two-level scan.
 //   k_om_ends     per tile of the sorted order: positives and group ends (a key that differs from its successor's; the last key of a
-//                 tile reads the first key of the next tile) -> counts [positives (tiles) | ends (tiles)], scanned by the same two kernels.
+//                 tile reads the first key of the next tile) -> counts [positives (tiles) | ends (tiles)], scanned by the sort's two-level
+//                 scan (k_ts_scan_chunks, k_ts_scan_short).
 //   k_om_walk     tp (inclusive positives) at every group end, fp = min(position + 1, valid) - tp, stored COMPACTED by the group's rank:
 //                 E[g] = (tp_g, fp_g).  A tie group may span any number of tiles; after the compaction the predecessor of group g is E[g-1].
 //   k_om_area     per 2048 groups: sum of (tp_g - tp_{g-1}) / n_pos * tp_g / (tp_g + fp_g) in double and of the INTEGER
@@ -26,23 +24,16 @@
 //                 n below ~1.3e8 whatever the labels; one rounding each for operands beyond), n_pos, n_neg.
 // Only (tp, fp) at group ends enter the areas, so the order inside a tie group is free and the payload is one bit.
 // Bound: HBM (a pass of the sort moves 14 bytes per key; four passes + 8 bytes per group for the compaction).
-#include "pdfops_common.h"
+#include "tile_sort.h"
 
 namespace {
 
-constexpr int LB = 256;
-constexpr int ITEMS = 8;                 // keys per lane and tile: wave w owns 512 consecutive keys, round r the 64 at w * 512 + r * 64
-constexpr int TILE = LB * ITEMS;         // 2048
-constexpr int WAVES = LB / 64;
-constexpr int RADIX = 256;               // 8-bit digits, four passes
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_CHUNK = LB * SCAN_ITEMS;   // 1024 words per workgroup of the first scan level
+using namespace tile_sort;   // LB, ITEMS, TILE, WAVES, RADIX, pos, scanned, chunks: the sort's tile geometry is this pass's too
+
 constexpr int HB = 512;                  // partial histogram rows (workgroups of k_om_keys)
 constexpr int MAXK = 1024;               // classes: 3 k + 3 LDS counters
 constexpr unsigned LAST_KEY = 0xFFFFFFFFu;
 typedef unsigned long long u64;
-
-__device__ __forceinline__ size_t om_pos(int tile, int w, int r, int lane) { return (size_t)tile * TILE + w * (ITEMS * 64) + r * 64 + lane; }
 
 __device__ __forceinline__ unsigned om_key(float s) {
     unsigned u = __float_as_uint(s);
@@ -128,116 +119,6 @@ __global__ __launch_bounds__(LB) void k_om_sums(int k, int nrows, const unsigned
     }
 }
 
-// hist[digit * ntiles + tile] = number of keys of the tile with that digit (integer LDS counters: the result does not depend on the order
-// of arrival)
-__global__ __launch_bounds__(LB) void k_om_hist(long n, int ntiles, int shift, const unsigned *__restrict__ keys, unsigned *__restrict__ hist) {
-    __shared__ unsigned h[RADIX];
-    const int tile = blockIdx.x;
-    h[threadIdx.x] = 0u;
-    __syncthreads();
-    for (int i = 0; i < ITEMS; ++i) {
-        const size_t p = (size_t)tile * TILE + i * LB + threadIdx.x;
-        if (p < (size_t)n) atomicAdd(&h[(keys[p] >> shift) & (RADIX - 1)], 1u);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * ntiles + tile] = h[threadIdx.x];
-}
-
-// exclusive scan of the workgroup's 256 values (lane order); `s` = 256 words of LDS, free on entry, free again after the call
-__device__ __forceinline__ unsigned om_block_excl_scan(unsigned v, unsigned *s) {
-    unsigned x = v;
-    s[threadIdx.x] = x;
-    __syncthreads();
-    for (int o = 1; o < LB; o <<= 1) {
-        const unsigned y = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0u;
-        __syncthreads();
-        x += y;
-        s[threadIdx.x] = x;
-        __syncthreads();
-    }
-    return x - v;
-}
-
-// first level, in place: data[e] -> sum of the chunk's words before e; gtot[chunk] = the chunk's sum
-__global__ __launch_bounds__(LB) void k_om_scan_chunks(long len, unsigned *__restrict__ data, unsigned *__restrict__ gtot) {
-    __shared__ unsigned s[LB];
-    const long e0 = (long)blockIdx.x * SCAN_CHUNK + (long)threadIdx.x * SCAN_ITEMS;
-    unsigned v[SCAN_ITEMS], sum = 0u;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) { v[i] = e0 + i < len ? data[e0 + i] : 0u; sum += v[i]; }
-    unsigned run = om_block_excl_scan(sum, s);
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        if (e0 + i < len) data[e0 + i] = run;
-        run += v[i];
-    }
-    if (threadIdx.x == LB - 1) gtot[blockIdx.x] = run;
-}
-
-// second level, in place: gtot[chunk] -> sum of the chunks before it.  One workgroup, lane l the chunks [l * per, (l + 1) * per).
-__global__ __launch_bounds__(LB) void k_om_scan_totals(long nchunks, unsigned *__restrict__ gtot) {
-    __shared__ unsigned s[LB];
-    const long per = (nchunks + LB - 1) / LB;
-    const long t0 = min(nchunks, (long)threadIdx.x * per), t1 = min(nchunks, t0 + per);
-    unsigned sum = 0u;
-    for (long t = t0; t < t1; ++t) sum += gtot[t];
-    unsigned run = om_block_excl_scan(sum, s);
-    for (long t = t0; t < t1; ++t) { const unsigned v = gtot[t]; gtot[t] = run; run += v; }
-}
-
-__device__ __forceinline__ unsigned om_scanned(const unsigned *data, const unsigned *gtot, size_t e) { return data[e] + gtot[e / SCAN_CHUNK]; }
-
-// stable scatter of one tile: position = start of the (digit, tile) group + keys of that digit in the tile's earlier waves + in the wave's
-// earlier rounds + among the round's lower lanes.
-__global__ __launch_bounds__(LB) void k_om_scatter(long n, int ntiles, int shift, const unsigned *__restrict__ keys_in,
-                                                   const unsigned char *__restrict__ pay_in, const unsigned *__restrict__ hist,
-                                                   const unsigned *__restrict__ gtot, unsigned *__restrict__ keys_out,
-                                                   unsigned char *__restrict__ pay_out) {
-    __shared__ unsigned cnt[WAVES][RADIX];
-    const int tile = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) cnt[i][threadIdx.x] = 0u;
-    __syncthreads();
-    unsigned key[ITEMS], off[ITEMS];
-    unsigned char val[ITEMS];
-    const unsigned long long lower = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < ITEMS; ++r) {
-        const size_t p = om_pos(tile, w, r, lane);
-        const bool valid = p < (size_t)n;
-        key[r] = valid ? keys_in[p] : 0u;
-        val[r] = valid ? pay_in[p] : (unsigned char)0;
-        const unsigned d = (key[r] >> shift) & (RADIX - 1);
-        unsigned long long peers = __ballot(valid);   // lanes of the round with this lane's digit
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const unsigned before = valid ? cnt[w][d] : 0u;   // the wave's own counters: no other wave touches them
-        off[r] = before + (unsigned)__popcll(peers & lower);
-        __syncthreads();
-        if (valid && (peers & lower) == 0ull) cnt[w][d] = before + (unsigned)__popcll(peers);   // the group's lowest lane
-        __syncthreads();
-    }
-    {   // lane = digit: the waves' counts become the waves' starting positions
-        unsigned run = om_scanned(hist, gtot, (size_t)threadIdx.x * ntiles + tile);
-#pragma unroll
-        for (int i = 0; i < WAVES; ++i) { const unsigned v = cnt[i][threadIdx.x]; cnt[i][threadIdx.x] = run; run += v; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ITEMS; ++r) {
-        if (om_pos(tile, w, r, lane) < (size_t)n) {
-            const unsigned q = cnt[w][(key[r] >> shift) & (RADIX - 1)] + off[r];   // < n: the (digit, tile) groups partition the n keys
-            if ((size_t)q >= (size_t)n) continue;                                    // (never taken; no store outside the buffers whatever happens)
-            keys_out[q] = key[r];
-            pay_out[q] = val[r];
-        }
-    }
-}
-
 // the last position of a group of equal keys (the array's last position is one)
 __device__ __forceinline__ bool om_is_end(const unsigned *keys, size_t p, long n) { return p + 1 == (size_t)n || keys[p + 1] != keys[p]; }
 
@@ -274,7 +155,7 @@ __global__ __launch_bounds__(LB) void k_om_walk(long n, int ntiles, const unsign
     unsigned mp = 0u, me = 0u;
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
-        const size_t p = om_pos(tile, w, r, lane);
+        const size_t p = pos(tile, w, r, lane);
         const bool valid = p < (size_t)n;
         posm[r] = __ballot(valid && pay[p] != 0);
         endm[r] = __ballot(valid && om_is_end(keys, p, n));
@@ -284,13 +165,13 @@ __global__ __launch_bounds__(LB) void k_om_walk(long n, int ntiles, const unsign
     if (lane == 0) { wtot[0][w] = mp; wtot[1][w] = me; }
     __syncthreads();
     const unsigned n_pos = (unsigned)totals[0], n_valid = (unsigned)totals[1];
-    unsigned runp = om_scanned(tcnt, gtot, (size_t)tile), rune = om_scanned(tcnt, gtot, (size_t)ntiles + tile) - n_pos;
+    unsigned runp = scanned(tcnt, gtot, (size_t)tile), rune = scanned(tcnt, gtot, (size_t)ntiles + tile) - n_pos;
     for (int i = 0; i < w; ++i) { runp += wtot[0][i]; rune += wtot[1][i]; }
     const unsigned long long lower = (1ull << lane) - 1ull, upto = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull;
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
         if ((endm[r] >> lane) & 1ull) {
-            const size_t p = om_pos(tile, w, r, lane);
+            const size_t p = pos(tile, w, r, lane);
             const unsigned tp = runp + (unsigned)__popcll(posm[r] & upto), rank = rune + (unsigned)__popcll(endm[r] & lower);
             const unsigned seen = p + 1 < (size_t)n_valid ? (unsigned)(p + 1) : n_valid;   // the ignored rows sit behind the valid ones
             if ((size_t)rank < (size_t)n) ends[rank] = make_uint2(tp, seen - tp);           // (there are at most n groups)
@@ -355,8 +236,6 @@ __global__ __launch_bounds__(LB) void k_om_final(int ntiles, const double *__res
     record[3] = (double)n_neg;
 }
 
-inline size_t om_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct OmWorkspace {
     unsigned *part, *keys[2], *hist, *gtot, *tcnt;
     unsigned char *pay[2];
@@ -366,24 +245,21 @@ struct OmWorkspace {
     size_t bytes;
 };
 
-inline size_t om_chunks(size_t words) { return (words + SCAN_CHUNK - 1) / SCAN_CHUNK; }
-
 OmWorkspace om_carve(char *base, long n) {
     const size_t nt = (size_t)((n + TILE - 1) / TILE), nn = (size_t)n;
     OmWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t b) { char *p = reinterpret_cast<char *>(reinterpret_cast<uintptr_t>(base) + o); o += om_align(b); return p; };
-    w.totals = reinterpret_cast<u64 *>(take(4 * sizeof(u64)));
-    w.pa = reinterpret_cast<double *>(take(nt * sizeof(double)));
-    w.ps = reinterpret_cast<u64 *>(take(nt * sizeof(u64)));
-    w.ends = reinterpret_cast<uint2 *>(take(nn * sizeof(uint2)));
-    w.part = reinterpret_cast<unsigned *>(take((size_t)(3 * MAXK + 3) * HB * 4));
-    for (int i = 0; i < 2; ++i) w.keys[i] = reinterpret_cast<unsigned *>(take(nn * 4));
-    w.hist = reinterpret_cast<unsigned *>(take(nt * RADIX * 4));
-    w.gtot = reinterpret_cast<unsigned *>(take(om_chunks(nt * RADIX) * 4));   // (RADIX >= 2: covers the scan of the 2 * tiles end counts too)
-    w.tcnt = reinterpret_cast<unsigned *>(take(2 * nt * 4));
-    for (int i = 0; i < 2; ++i) w.pay[i] = reinterpret_cast<unsigned char *>(take(nn));
-    w.bytes = o;
+    PdfCarver ws{base};
+    w.totals = ws.take<u64>(4);
+    w.pa = ws.take<double>(nt);
+    w.ps = ws.take<u64>(nt);
+    w.ends = ws.take<uint2>(nn);
+    w.part = ws.take<unsigned>((size_t)(3 * MAXK + 3) * HB);
+    for (int i = 0; i < 2; ++i) w.keys[i] = ws.take<unsigned>(nn);
+    w.hist = ws.take<unsigned>(nt * RADIX);
+    w.gtot = ws.take<unsigned>(chunks(nt * RADIX));   // (RADIX >= 2: covers the scan of the 2 * tiles end counts too)
+    w.tcnt = ws.take<unsigned>(2 * nt);
+    for (int i = 0; i < 2; ++i) w.pay[i] = ws.take<unsigned char>(nn);
+    w.bytes = ws.off;
     return w;
 }
 
@@ -409,18 +285,11 @@ extern "C" int pdf_openset_metrics(long n, int c, const float *logits, const lon
     k_om_keys<<<(unsigned)rows, LB, 0, s>>>(n, c, k, nt, logits, pred, score, target, ignore, unknown, w.keys[0], w.pay[0], w.part);
     k_om_sums<<<(unsigned)(k + 1), LB, 0, s>>>(k, rows, w.part, hist, w.totals, record, score != nullptr);
     if (!score) return pdf_launch_status();
-    const long hlen = (long)nt * RADIX, hchunks = (long)om_chunks((size_t)hlen);
-    int cur = 0;
-    for (int shift = 0; shift < 32; shift += 8, cur ^= 1) {   // four passes, whatever the data: nothing is decided on the host
-        k_om_hist<<<(unsigned)nt, LB, 0, s>>>(n, nt, shift, w.keys[cur], w.hist);
-        k_om_scan_chunks<<<(unsigned)hchunks, LB, 0, s>>>(hlen, w.hist, w.gtot);
-        k_om_scan_totals<<<1, LB, 0, s>>>(hchunks, w.gtot);
-        k_om_scatter<<<(unsigned)nt, LB, 0, s>>>(n, nt, shift, w.keys[cur], w.pay[cur], w.hist, w.gtot, w.keys[cur ^ 1], w.pay[cur ^ 1]);
-    }
-    const long tlen = 2L * nt, tchunks = (long)om_chunks((size_t)tlen);
+    const int cur = sort<unsigned char, true>(n, 1, w.keys, w.pay, w.hist, w.gtot, s);
+    const long tlen = 2L * nt, tchunks = (long)chunks((size_t)tlen);
     k_om_ends<<<(unsigned)nt, LB, 0, s>>>(n, nt, w.keys[cur], w.pay[cur], w.tcnt);
-    k_om_scan_chunks<<<(unsigned)tchunks, LB, 0, s>>>(tlen, w.tcnt, w.gtot);
-    k_om_scan_totals<<<1, LB, 0, s>>>(tchunks, w.gtot);
+    k_ts_scan_chunks<<<(unsigned)tchunks, LB, 0, s>>>(tlen, w.tcnt, w.gtot);
+    k_ts_scan_short<<<1, LB, 0, s>>>((int)tchunks, w.gtot, nullptr);
     k_om_walk<<<(unsigned)nt, LB, 0, s>>>(n, nt, w.keys[cur], w.pay[cur], w.tcnt, w.gtot, w.totals, w.ends);
     k_om_area<<<(unsigned)nt, LB, 0, s>>>(n, w.ends, w.totals, w.pa, w.ps);
     k_om_final<<<1, LB, 0, s>>>(nt, w.pa, w.ps, w.totals, record);

@@ -32,6 +32,19 @@ static inline bool pdf_lds_limit_raised(PdfLdsLimit &site, const void *kernel, i
 
 static inline int pdf_divup(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Carves a caller's workspace into arrays that each start on a 256-byte boundary.  With base == nullptr it only adds up: `off` after the
+// last take is the size the workspace needs.
+struct PdfCarver {
+    char *base;
+    size_t off = 0;
+    template <typename T>
+    T *take(size_t count) {
+        T *p = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + off);
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
 // Cap for grid-stride launches of the HBM-bound kernels: 256 CUs x 8 resident blocks.
 #define PDF_MAX_BLOCKS 2048
 

@@ -25,7 +25,7 @@ import numpy as np  # noqa: E402
 K = 13
 UNKNOWN = (5, 9)
 IGNORE = -1
-TILE, SCAN_CHUNK, RADIX = 2048, 1024, 256      # csrc/openset_metrics.hip: keys per sort tile, words per first-level scan workgroup, digits
+TILE, SCAN_CHUNK, RADIX = 2048, 1024, 256      # csrc/tile_sort.h: keys per sort tile, words per first-level scan workgroup, digits
 # The (digit, tile) scan has one word per digit and tile: its second level (one workgroup, 256 lanes) gives a lane more than one chunk once
 # there are more than 256 chunks, i.e. more than 256 * SCAN_CHUNK / RADIX = 1024 tiles = 2,097,152 rows.
 DEEP = TILE * (256 * SCAN_CHUNK // RADIX) + 1

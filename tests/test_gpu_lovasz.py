@@ -18,12 +18,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 IGNORE = -1
-TILE = 2048          # csrc/lovasz.hip: keys per sort tile
+TILE = 2048          # csrc/tile_sort.h: keys per sort tile
 STAGE_TOL = 1e-5     # of the largest magnitude
 E2E_TOL = 1e-4
 GAP_ULP = 16
 
-# name: (N, C, seed, options).  N: 1, 2, around the wave (63 / 64 / 65), 257, one row more than a sort tile, two tiles + 3, 20,000.
+# name: (N, C, seed, options).  N: 1, 2, around the wave (63 / 64 / 65), 257, around a sort tile (2047 / 2048 / 2049), exactly two tiles,
+# two tiles + 3, 20,000.
 # options: absent = classes without a row, ignored = share of ignored rows, seen = class_seen, single = (class, row) with ONE
 # foreground row, only = every row has this class
 CASES = {
@@ -35,7 +36,10 @@ CASES = {
     "n257_c13_absent": (257, 13, 37, {"absent": (5, 9), "ignored": 0.1}),
     "n257_c64": (257, 64, 37, {}),
     "n300_c14_only": (300, 14, 1138, {"only": 6}),
+    "n2047_c13": (TILE - 1, 13, 45, {}),
+    "n2048_c13": (TILE, 13, 46, {}),
     "n2049_c13_ignored": (TILE + 1, 13, 39, {"ignored": 0.1}),
+    "n4096_c3_ignored": (2 * TILE, 3, 47, {"ignored": 0.1}),
     "n4099_c14_seen": (2 * TILE + 3, 14, 40, {"seen": (0, 2, 3, 7, 13), "ignored": 0.1}),
     "n4099_c64": (2 * TILE + 3, 64, 41, {"absent": (11,)}),
     "n20000_c20": (20000, 20, 42, {"ignored": 0.1, "absent": (17,), "single": (4, 12345)}),

@@ -49,7 +49,7 @@ def unknown_bytes(mod):
     return m.cuda()
 
 
-# csrc/openset_metrics.hip: TILE = 2048 keys per sort tile, SCAN_CHUNK = 1024 words per workgroup of the first scan level, 256 lanes in
+# csrc/tile_sort.h: TILE = 2048 keys per sort tile, SCAN_CHUNK = 1024 words per workgroup of the first scan level, 256 lanes in
 # the second: "deep_scan" (2048 * 1024 + 1 rows) is the first size at which a lane of the second level owns more than one chunk;
 # every case above 4 tiles (1024 / 256 digits) runs both levels.
 def test_every_fixture_case_through_the_c_abi(cases, lib):

@@ -7,9 +7,9 @@ pass is slower than the composition (`within_bound`) or the two losses differ by
 
 How the time is taken: one process, every sample is forward + backward between two HIP events, the variants alternate inside every round;
 reported per variant: median, min and the 10th / 90th percentile over the rounds after a warm-up.  `fused_abi` is the forward entry
-alone (pdf_lovasz_forward on preallocated buffers).  `sort_share`: the share of the k_lv_hist / k_lv_scan / k_lv_scatter kernels in the
-device time of the pass's kernels, from a torch.profiler trace of a few extra calls (information only; "not measured" when the profiler
-reports no kernels).
+alone (pdf_lovasz_forward on preallocated buffers).  `sort_share`: the share of the sort's kernels (csrc/tile_sort.h: k_ts_hist /
+k_ts_scan_segments / k_ts_scatter) in the device time of the pass's kernels (k_lv_* and k_ts_*), from a torch.profiler trace of a few
+extra calls (information only; "not measured" when the profiler reports no kernels).
 
 ``--step``: information only -- the captured config-2 training step (2 x 100k points, Seg50, 6 channels, 13 classes, the stand-in pseudo
 mask) with CrossEntropyLoss + LovaszLoss in both criteria lists, and with CrossEntropyLoss alone, each in a child process of its own.
@@ -112,13 +112,14 @@ def sort_share(run):
             torch.cuda.synchronize()
         tot, sort, per = 0.0, 0.0, {}
         for ev in prof.key_averages():
-            if "k_lv_" not in ev.key:
+            at = max(ev.key.find("k_lv_"), ev.key.find("k_ts_"))   # the pass's own kernels and the shared sort's
+            if at < 0:
                 continue
             t = float(getattr(ev, "device_time_total", 0.0) or getattr(ev, "cuda_time_total", 0.0))
-            name = ev.key[ev.key.index("k_lv_"):].split("(")[0].split("<")[0]
+            name = ev.key[at:].split("(")[0].split("<")[0]
             per[name] = round(per.get(name, 0.0) + t / 5, 2)
             tot += t
-            if any(s in ev.key for s in ("k_lv_hist", "k_lv_scan", "k_lv_scatter")):
+            if name in ("k_ts_hist", "k_ts_scan_segments", "k_ts_scatter"):
                 sort += t
         if tot <= 0:
             return "not measured"

@@ -6,8 +6,8 @@ their host reads), at three sizes: the tester bench's scene (374,732 rows), 1,00
 exits non-zero when the pass is slower than the composition at any size (bound: ratio <= 1.0) or the two disagree.
 
 Timing: one process, HIP events around each call (both variants end with their result on the host), the variants alternating inside every
-round, the median of the rounds after the warm-up ones.  `kernels`: the pass's per-kernel split of one call (torch profiler, 1,000,000
-rows; information only).
+round, the median of the rounds after the warm-up ones.  `kernels`: the pass's per-kernel split of one call (its own k_om_* kernels and
+the k_ts_* ones of csrc/tile_sort.h; torch profiler, 1,000,000 rows; information only).
 
 `--tester`: additionally times `testing.OpenSegTester.test` on the synthetic scene of tools/tester_bench.py (Seg50, MSP scores; the whole
 call, metrics included; synchronised wall time, one warm-up) in a child process of its own, and with `--baseline-tree PATH` (a checkout
@@ -99,10 +99,11 @@ def kernel_split(run, calls=5):
             torch.cuda.synchronize()
         per = {}
         for ev in prof.key_averages():
-            if "k_om_" not in ev.key:
+            at = max(ev.key.find("k_om_"), ev.key.find("k_ts_"))   # the pass's own kernels and the shared sort's
+            if at < 0:
                 continue
             t = float(getattr(ev, "device_time_total", 0.0) or getattr(ev, "cuda_time_total", 0.0))
-            name = ev.key[ev.key.index("k_om_"):].split("(")[0].split("<")[0]
+            name = ev.key[at:].split("(")[0].split("<")[0]
             per[name] = round(per.get(name, 0.0) + t / calls, 2)
         if not per:
             return "not measured"
