@@ -45,8 +45,9 @@ extern "C" {
  * 9 = pdf_radius_neighbors_self_adaptive added (no existing parameter list changed);
  * 10 = pdf_lovasz_workspace_bytes / pdf_lovasz_forward / pdf_lovasz_backward added (no existing parameter list changed);
  * 11 = pdf_openset_metrics_workspace_bytes / pdf_openset_metrics added (no existing parameter list changed);
- * 12 = pdf_scene_bounds / pdf_window_keys_scene added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 12
+ * 12 = pdf_scene_bounds / pdf_window_keys_scene added (no existing parameter list changed);
+ * 13 = pdf_criteria_workspace_floats / pdf_ce_ex_* / pdf_focal_* / pdf_dice_* / pdf_bfocal_* added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 13
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -377,6 +378,48 @@ long pdf_ce_workspace_floats(void);
 int pdf_ce_forward(long n, int c, const float *logits, const long *target, long ignore, float *grad, float *acc, float *loss,
                    void *stream);
 int pdf_ce_backward(long n, int c, const float *dlogits, const float *acc, const float *gy, float *grad_out, void *stream);
+
+/* The remaining criteria of pointcept/models/losses/misc.py as capturable passes (csrc/criteria.hip): fp32 logits, int64 labels, no float
+ * atomics (per-workgroup partial sums in their own slots, added by one workgroup in a fixed order, in double: bit-reproducible), nothing
+ * to zero, no host read.  acc: pdf_criteria_workspace_floats(c) floats (c = 1 for the binary loss), 8-byte aligned; acc[0..2] receive
+ * [sum, normaliser, scale] where `scale` is what the backward multiplies with.  Every forward leaves its unscaled gradient (dice: the
+ * softmax) in a buffer the backward only reads, so a node can be differentiated more than once; grad_out may not alias it.
+ * PDF_REDUCE_*: the `reduction` argument.  n < 1, c < 1, a NULL array, an unknown reduction, label_smoothing outside [0, 1]:
+ * PDF_ERR_BAD_ARG before any launch. */
+#define PDF_REDUCE_NONE 0
+#define PDF_REDUCE_MEAN 1
+#define PDF_REDUCE_SUM 2
+long pdf_criteria_workspace_floats(int c);
+/* nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing) over (n, c) logits, any c >= 1 (c <= 64: one lane per row; above:
+ * one wave per row).  weight: (c) floats or NULL (all 1).  Row with label t != ignore: l = (1 - eps) w[t] (-lp[t]) + eps / c sum_j w[j]
+ * (-lp[j]), lp = log_softmax.  mean: loss[0] = sum l / sum w[t] (NaN when no row is counted); sum: loss[0] = sum l; none: loss (n) = l,
+ * 0 on ignored rows.  A label that is neither `ignore` nor in [0, c) makes the loss (none: its row) NaN; its gradient row is 0.
+ * grad (n*c) = d l / d logits.  Backward: grad_out = dlogits * gy[0] * acc[2] (none: * gy[row], gy (n)). */
+int pdf_ce_ex_forward(long n, int c, const float *logits, const long *target, const float *weight, float label_smoothing, int reduction,
+                      long ignore, float *grad, float *acc, float *loss, void *stream);
+int pdf_ce_ex_backward(long n, int c, const float *dlogits, const float *acc, const float *gy, int reduction, float *grad_out, void *stream);
+/* FocalLoss (misc.py:97-172) over the rows with target != ignore: per element of the one-hot target t against x = logits,
+ * BCE_with_logits(x, t) * (alpha t + (1 - alpha)(1 - t)) * (t ? 1 - sigmoid(x) : sigmoid(x)) ^ gamma; alpha_vec: (c) floats or NULL (then
+ * the scalar alpha).  mean: over (valid rows * c) elements, counted on the device, 0 with a zero gradient when every row is ignored; sum
+ * likewise (PDF_REDUCE_NONE: PDF_ERR_BAD_ARG).  A bad label makes the loss NaN.  Backward: grad_out = dlogits * gy[0] * acc[2]. */
+int pdf_focal_forward(long n, int c, const float *logits, const long *target, const float *alpha_vec, float alpha, float gamma, int reduction,
+                      long ignore, float *grad, float *acc, float *loss, void *stream);
+int pdf_focal_backward(long n, int c, const float *dlogits, const float *acc, const float *gy, float *grad_out, void *stream);
+/* DiceLoss (misc.py:176-223), loss_weight 1: over the rows with target != ignore, p = softmax(logits), y = onehot(clamp(target, 0, c - 1))
+ * (labels are clamped, not refused: the reference's behaviour); per class i: num = 2 sum p_i y_i + smooth, den = sum (p_i ^ exponent + y_i)
+ * + smooth; loss[0] = sum_{i != ignore} (1 - num / den) / c (the divisor stays c when class `ignore` is skipped: the reference's
+ * behaviour).  prob (n*c) receives p; acc also keeps the per-class coefficients the backward reads.  exponent > 0 (2: a fast path).
+ * Backward: grad_out = d loss / d logits * gy[0], from prob, target and acc. */
+int pdf_dice_forward(long n, int c, const float *logits, const long *target, float smooth, float exponent, long ignore, float *prob,
+                     float *acc, float *loss, void *stream);
+int pdf_dice_backward(long n, int c, const float *prob, const long *target, long ignore, float exponent, const float *acc, const float *gy,
+                      float *grad_out, void *stream);
+/* BinaryFocalLoss (misc.py:60-93) over n elements with float targets (probabilities allowed): bce = logits ? BCE_with_logits(x, t) :
+ * BCE(x, t) (logs clamped at -100 as F.binary_cross_entropy); f = (alpha t + (1 - alpha)(1 - t)) (1 - exp(-bce)) ^ gamma bce.  reduce != 0:
+ * loss[0] = mean f; reduce == 0: loss (n) = f.  grad (n) = d f / d x.  Backward: grad_out = dpred * gy[0] * acc[2] (reduce == 0: * gy[e]). */
+int pdf_bfocal_forward(long n, const float *pred, const float *target, float alpha, float gamma, int logits, int reduce, float *grad,
+                       float *acc, float *loss, void *stream);
+int pdf_bfocal_backward(long n, const float *dpred, const float *acc, const float *gy, int reduce, float *grad_out, void *stream);
 
 /* Distillation loss of the incremental learner (pointcept/incrLearners/ours/pointpdf_incr_v1m1_base.py:62-87, IncrDistillKlLoss):
  * student (n, cs) and teacher (n, ct) fp32 logits, labels (n) int64, ct <= cs <= 64.  Target row t = [softmax(teacher * inv_tt), 0 ..]

@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 12   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 13   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -123,6 +123,15 @@ _HIP_ONLY_PROTOS = {
     "seg_sum_rows_own": "liipppifppp",
     "seg_sum_weighted": "liiippppip",
     "seg_sum_weighted_ordered": "liiippppipp",
+    # csrc/criteria.hip
+    "ce_ex_forward": "lipppfilppp",
+    "ce_ex_backward": "lipppip",
+    "focal_forward": "lipppffilppp",
+    "focal_backward": "lipppp",
+    "dice_forward": "lippfflppp",
+    "dice_backward": "lipplfppp",
+    "bfocal_forward": "lppffiippp",
+    "bfocal_backward": "lpppip",
 }
 _KIND = {"i": c_int, "l": c_long, "f": c_float, "d": c_double, "p": c_void_p}
 
@@ -676,6 +685,8 @@ class HipBackend(CBackend):
         lib.pdf_ce_forward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_ce_backward.restype = c_int
         lib.pdf_ce_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.pdf_criteria_workspace_floats.restype = c_long
+        lib.pdf_criteria_workspace_floats.argtypes = [c_int]
         lib.pdf_incr_kl_workspace_floats.restype = c_long
         lib.pdf_incr_kl_workspace_floats.argtypes = []
         lib.pdf_incr_kl_forward.restype = c_int
@@ -1830,6 +1841,117 @@ class HipBackend(CBackend):
         nul = ctypes.c_void_p(None)
         self._call("vote_accumulate", n, c, logits, nul if score is None else score, index, pred,
                    nul if score is None else score_sum, nul if score is None else score_cnt)
+
+    # -- criteria (csrc/criteria.hip; segmentor.CrossEntropyLoss and losses.py drive them) ----------------------------------------------
+    REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}   # include/pdfops.h: PDF_REDUCE_*
+
+    def _criteria_acc(self, like, c):
+        # every float is written before it is read (csrc/criteria.hip): nothing to zero, no memset node in a captured step
+        return self._new(like, (int(self.lib.pdf_criteria_workspace_floats(int(c))),), torch.float32)
+
+    @staticmethod
+    def _logits_labels(logits, target, what):
+        _check(logits, torch.float32, "logits"); _check(target, torch.int64, "target")
+        if logits.dim() != 2 or target.shape != (logits.shape[0],) or logits.shape[0] < 1 or logits.shape[1] < 1:
+            raise ValueError(f"{what}: logits (n, c) and target (n) expected, got {tuple(logits.shape)}, {tuple(target.shape)}")
+        return logits.shape
+
+    @staticmethod
+    def _class_vector(v, c, name):
+        if v is not None:
+            _check(v, torch.float32, name)
+            if v.shape != (c,):
+                raise ValueError(f"{name}: expected ({c},), got {tuple(v.shape)}")
+        return ctypes.c_void_p(None) if v is None else v
+
+    def ce_ex_forward(self, logits, target, weight, label_smoothing, reduction, ignore_index):
+        """-> loss (scalar, or (n) for "none"), dlogits (n, c) unscaled, acc.  nn.CrossEntropyLoss in full (include/pdfops.h)."""
+        n, c = self._logits_labels(logits, target, "ce_ex_forward")
+        w = self._class_vector(weight, c, "weight")
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+        require_current_device(logits, target, weight)
+        grad = self._new(logits, (n, c), torch.float32)
+        acc = self._criteria_acc(logits, c)
+        loss = self._new(logits, (n,) if reduction == "none" else (), torch.float32)
+        self._call("ce_ex_forward", n, c, logits, target, w, float(label_smoothing), self.REDUCTIONS[reduction], int(ignore_index), grad, acc, loss)
+        return loss, grad, acc
+
+    def ce_ex_backward(self, dlogits, acc, gy, reduction):
+        _check(dlogits, torch.float32, "dlogits"); _check(acc, torch.float32, "acc"); _check(gy, torch.float32, "grad_output")
+        n, c = dlogits.shape
+        if gy.numel() != (n if reduction == "none" else 1):
+            raise ValueError(f"ce_ex_backward: grad_output of {gy.numel()} elements for reduction {reduction!r} over {n} rows")
+        require_current_device(dlogits, acc, gy)
+        out = self._new(dlogits, (n, c), torch.float32)   # the saved buffer stays untouched (retain_graph)
+        self._call("ce_ex_backward", n, c, dlogits, acc, gy, self.REDUCTIONS[reduction], out)
+        return out
+
+    def focal_forward(self, logits, target, alpha, gamma, reduction, ignore_index):
+        """-> loss (scalar), dlogits (n, c) unscaled, acc.  ``alpha``: a float or a (c) fp32 tensor on the device."""
+        n, c = self._logits_labels(logits, target, "focal_forward")
+        if reduction not in ("mean", "sum"):
+            raise ValueError("focal_forward: reduction must be 'mean' or 'sum'")
+        vec = alpha if isinstance(alpha, torch.Tensor) else None
+        a = self._class_vector(vec, c, "alpha")
+        require_current_device(logits, target, vec)
+        grad = self._new(logits, (n, c), torch.float32)
+        acc = self._criteria_acc(logits, c)
+        loss = self._new(logits, (), torch.float32)
+        self._call("focal_forward", n, c, logits, target, a, 0.0 if vec is not None else float(alpha), float(gamma),
+                   self.REDUCTIONS[reduction], int(ignore_index), grad, acc, loss)
+        return loss, grad, acc
+
+    def focal_backward(self, dlogits, acc, gy):
+        _check(dlogits, torch.float32, "dlogits"); _check(acc, torch.float32, "acc"); _check(gy, torch.float32, "grad_output")
+        n, c = dlogits.shape
+        require_current_device(dlogits, acc, gy)
+        out = self._new(dlogits, (n, c), torch.float32)
+        self._call("focal_backward", n, c, dlogits, acc, gy, out)
+        return out
+
+    def dice_forward(self, logits, target, smooth, exponent, ignore_index):
+        """-> loss (scalar, loss_weight 1), prob (n, c), acc (keeps the class coefficients the backward reads)."""
+        n, c = self._logits_labels(logits, target, "dice_forward")
+        if not float(exponent) > 0.0:
+            raise ValueError(f"dice_forward: exponent must be positive, got {exponent}")
+        require_current_device(logits, target)
+        prob = self._new(logits, (n, c), torch.float32)
+        acc = self._criteria_acc(logits, c)
+        loss = self._new(logits, (), torch.float32)
+        self._call("dice_forward", n, c, logits, target, float(smooth), float(exponent), int(ignore_index), prob, acc, loss)
+        return loss, prob, acc
+
+    def dice_backward(self, prob, target, ignore_index, exponent, acc, gy):
+        n, c = self._logits_labels(prob, target, "dice_backward")
+        _check(acc, torch.float32, "acc"); _check(gy, torch.float32, "grad_output")
+        require_current_device(prob, target, acc, gy)
+        out = self._new(prob, (n, c), torch.float32)
+        self._call("dice_backward", n, c, prob, target, int(ignore_index), float(exponent), acc, gy, out)
+        return out
+
+    def bfocal_forward(self, pred, target, alpha, gamma, logits, reduce):
+        """-> loss (scalar, or (n) with reduce=False), dpred (n) unscaled, acc.  pred, target: flat fp32."""
+        _check(pred, torch.float32, "pred"); _check(target, torch.float32, "target")
+        if pred.dim() != 1 or target.shape != pred.shape or pred.shape[0] < 1:
+            raise ValueError(f"bfocal_forward: pred (n) and target (n) expected, got {tuple(pred.shape)}, {tuple(target.shape)}")
+        require_current_device(pred, target)
+        n = pred.shape[0]
+        grad = self._new(pred, (n,), torch.float32)
+        acc = self._criteria_acc(pred, 1)
+        loss = self._new(pred, () if reduce else (n,), torch.float32)
+        self._call("bfocal_forward", n, pred, target, float(alpha), float(gamma), int(bool(logits)), int(bool(reduce)), grad, acc, loss)
+        return loss, grad, acc
+
+    def bfocal_backward(self, dpred, acc, gy, reduce):
+        _check(dpred, torch.float32, "dpred"); _check(acc, torch.float32, "acc"); _check(gy, torch.float32, "grad_output")
+        n = dpred.shape[0]
+        if gy.numel() != (1 if reduce else n):
+            raise ValueError(f"bfocal_backward: grad_output of {gy.numel()} elements for reduce={reduce} over {n} elements")
+        require_current_device(dpred, acc, gy)
+        out = self._new(dpred, (n,), torch.float32)
+        self._call("bfocal_backward", n, dpred, acc, gy, int(bool(reduce)), out)
+        return out
 
     # -- batched test-time fragments (csrc/fragments.hip; pointcloudpdf_amd/testing.py drives them) ------------------------------------
     @staticmethod

@@ -54,3 +54,15 @@ def register_losses_into_pointcept(force=True):
     from .registry import LOSSES
 
     PC_LOSSES.register_module(name="LovaszLoss", force=force, module=LOSSES.get("LovaszLoss"))
+
+
+def register_criteria_into_pointcept(force=True, cross_entropy=True):
+    """The criteria of the reference's losses/misc.py likewise: ``FocalLoss``, ``DiceLoss``, ``BinaryFocalLoss`` (losses.py) and, unless
+    ``cross_entropy=False``, ``CrossEntropyLoss`` (segmentor.py: class weights, label smoothing, every reduction and any class count as
+    capturable HIP passes; the reference's own class stays usable, through torch's kernels)."""
+    from pointcept.models.losses.builder import LOSSES as PC_LOSSES  # noqa: import error = pointcept not importable
+    from . import losses, segmentor  # noqa: F401  (fill the registry)
+    from .registry import LOSSES
+
+    for name in ["FocalLoss", "DiceLoss", "BinaryFocalLoss"] + (["CrossEntropyLoss"] if cross_entropy else []):
+        PC_LOSSES.register_module(name=name, force=force, module=LOSSES.get(name))

@@ -1,4 +1,6 @@
-"""Lovasz loss -- pointcept/models/losses/lovasz.py (``LovaszLoss``; Berman et al., "The Lovasz-Softmax loss", CVPR 2018), the second
+"""Criteria beyond the plain cross-entropy: the Lovasz loss (below) and FocalLoss / DiceLoss / BinaryFocalLoss (second half of this file).
+
+Lovasz loss -- pointcept/models/losses/lovasz.py (``LovaszLoss``; Berman et al., "The Lovasz-Softmax loss", CVPR 2018), the second
 criterion of the reference's segmentation recipes: ``dict(type="LovaszLoss", mode="multiclass", loss_weight=1.0, ignore_index=-1)``.
 
 ``mode="multiclass"`` over (N, C) logits and (N,) int64 labels, the form every point-cloud config uses:
@@ -29,6 +31,7 @@ point clouds.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .dense import _amp_bwd, _amp_fwd   # (custom nodes keep fp32 tensors under autocast: dense.py)
 from .registry import LOSSES
@@ -185,3 +188,250 @@ class LovaszLoss(nn.Module):
         else:
             loss = lovasz_softmax_reference(y_pred, y_true, self.ignore_index, self.class_seen)
         return loss * self.loss_weight
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# FocalLoss, DiceLoss, BinaryFocalLoss -- pointcept/models/losses/misc.py:60-223, with the reference's constructors (and its assertions
+# on argument types).  On the device (fp32 logits, int64 labels) each runs as one capturable pass of csrc/criteria.hip; everywhere else as
+# the ``*_reference`` composition below, which is also the independent side of the tests.  The reference selects rows with a boolean mask
+# (``pred[valid_mask]``) and branches on ``len(target) == 0``: both read the device back, so its forwards cannot sit in a captured step.
+# The compositions use ``where`` and counts instead, and add their sums in float64 when the input is float32 (the kernels do the same);
+# everything elementwise stays in the input's dtype.
+#
+# Choices of this package where the reference is silent or broken:
+#
+# * FocalLoss with every row ignored: a scalar 0 tensor with a zero gradient (the reference returns the python float 0.0, a host branch);
+# * FocalLoss(reduction="sum"): the reference calls ``Tensor.total`` there and raises AttributeError on every call; built to the evident
+#   formula (the sum of the terms the mean averages);
+# * FocalLoss with a label that is neither ``ignore_index`` nor a class id: NaN, as the fused cross-entropy (the reference's one_hot raises);
+# * DiceLoss keeps the reference's two quirks: labels are CLAMPED into [0, C - 1], not refused, and class ``i == ignore_index`` is left out
+#   of the sum while the divisor stays C (with the default -1 nothing is left out); rows whose label equals ignore_index are dropped;
+# * SmoothCELoss is not provided: the reference's forward raises AttributeError on every call (``Tensor.total``), no config can use it;
+#   ``CrossEntropyLoss(label_smoothing=...)`` covers the intent.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _acc_dtype(t):
+    return torch.float64 if t.dtype == torch.float32 else t.dtype
+
+
+def _rows_2d(pred, target):
+    """misc.py:133-143: (B, C, d1, ...) -> (N, C), the target flattened."""
+    if pred.dim() != 2:
+        pred = pred.transpose(0, 1)
+        pred = pred.reshape(pred.size(0), -1).transpose(0, 1)
+    target = target.reshape(-1)
+    assert pred.size(0) == target.size(0), "The shape of pred doesn't match the shape of target"
+    return pred.contiguous(), target.contiguous()
+
+
+def focal_loss_reference(pred, target, gamma=2.0, alpha=0.5, reduction="mean", ignore_index=-1):
+    """FocalLoss (loss_weight 1) over (N, C) logits without mask indexing or host branches.  ``alpha``: float, list or (C) tensor."""
+    c = pred.shape[1]
+    valid = target != ignore_index
+    bad = valid & ((target < 0) | (target >= c))
+    t = F.one_hot(target.clamp(0, c - 1), num_classes=c).to(pred.dtype)
+    if isinstance(alpha, (list, tuple)):
+        alpha = pred.new_tensor(alpha)
+    elif isinstance(alpha, torch.Tensor):
+        alpha = alpha.to(pred.dtype)
+    sig = pred.sigmoid()
+    one_minus_pt = (1 - sig) * t + sig * (1 - t)
+    focal_weight = (alpha * t + (1 - alpha) * (1 - t)) * one_minus_pt.pow(gamma)
+    loss = F.binary_cross_entropy_with_logits(pred, t, reduction="none") * focal_weight
+    loss = torch.where(valid[:, None], loss, torch.zeros_like(loss))
+    total = loss.to(_acc_dtype(pred)).sum()
+    if reduction == "mean":
+        count = valid.sum() * c
+        total = torch.where(count > 0, total / count.clamp(min=1), torch.zeros_like(total))
+    elif reduction != "sum":
+        raise ValueError(f"FocalLoss: reduction {reduction!r}")
+    total = torch.where(bad.any(), torch.full_like(total, float("nan")), total)
+    return total.to(pred.dtype)
+
+
+def dice_loss_reference(pred, target, smooth=1, exponent=2, ignore_index=-1):
+    """DiceLoss (loss_weight 1) over (N, C) logits: labels clamped, class ``ignore_index`` skipped with the divisor left at C."""
+    c = pred.shape[1]
+    valid = (target != ignore_index)[:, None]
+    p = F.softmax(pred, dim=1)
+    y = F.one_hot(target.clamp(0, c - 1), num_classes=c).to(p.dtype)
+    zero = torch.zeros_like(p)
+    acc = _acc_dtype(p)
+    inter = torch.where(valid, p * y, zero).to(acc).sum(0)
+    mass = torch.where(valid, p.pow(exponent) + y, zero).to(acc).sum(0)   # y is 0 / 1: y ** exponent == y
+    term = 1 - (2 * inter + smooth) / (mass + smooth)
+    keep = torch.arange(c, device=pred.device) != ignore_index
+    return (torch.where(keep, term, torch.zeros_like(term)).sum() / c).to(p.dtype)
+
+
+def binary_focal_loss_reference(pred, target, gamma=2.0, alpha=0.5, logits=True, reduce=True):
+    """BinaryFocalLoss (loss_weight 1), elementwise over float targets; ``reduce`` -> the mean."""
+    target = target.to(pred.dtype)
+    if logits:
+        bce = F.binary_cross_entropy_with_logits(pred, target, reduction="none")
+    else:
+        bce = F.binary_cross_entropy(pred, target, reduction="none")
+    pt = torch.exp(-bce)
+    focal = (alpha * target + (1 - alpha) * (1 - target)) * (1 - pt) ** gamma * bce
+    if reduce:
+        focal = (focal.to(_acc_dtype(pred)).sum() / focal.numel()).to(pred.dtype)
+    return focal
+
+
+def _upload_once(cache, key, make, what):
+    """A small host constant as a device tensor, uploaded once per key.  The upload is a host-to-device copy, which must not be recorded
+    into a stream capture: the first call has to be an eager one (``LovaszLoss._class_mask``)."""
+    if key not in cache:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what} has not been uploaded to {key[0]} yet and the stream is capturing; run one eager forward on this "
+                               "device before the capture")
+        cache[key] = make()
+    return cache[key]
+
+
+class _FusedFocal(torch.autograd.Function):
+    """FocalLoss over (N, C) fp32 logits as one pass of csrc/criteria.hip; the backward is a scaled copy that only reads the saved buffer."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, pred, target, alpha, gamma, reduction, ignore):
+        from . import _native
+
+        loss, dlogits, acc = _native.hip_backend().focal_forward(pred, target, alpha, gamma, reduction, ignore)
+        ctx.save_for_backward(dlogits, acc)
+        return loss
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy):
+        from . import _native
+
+        dlogits, acc = ctx.saved_tensors
+        return _native.hip_backend().focal_backward(dlogits, acc, gy.contiguous().float()), None, None, None, None, None
+
+
+class _FusedDice(torch.autograd.Function):
+    """DiceLoss over (N, C) fp32 logits: softmax + column sums + class terms forward, a second row pass backward (csrc/criteria.hip)."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, pred, target, smooth, exponent, ignore):
+        from . import _native
+
+        loss, prob, acc = _native.hip_backend().dice_forward(pred, target, smooth, exponent, ignore)
+        ctx.save_for_backward(prob, target, acc)
+        ctx.cfg = (exponent, ignore)
+        return loss
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy):
+        from . import _native
+
+        prob, target, acc = ctx.saved_tensors
+        exponent, ignore = ctx.cfg
+        return _native.hip_backend().dice_backward(prob, target, ignore, exponent, acc, gy.contiguous().float()), None, None, None, None
+
+
+class _FusedBinaryFocal(torch.autograd.Function):
+    """BinaryFocalLoss over flat fp32 predictions and float targets as one elementwise pass (csrc/criteria.hip); gradient with respect to
+    the prediction only."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, pred, target, alpha, gamma, logits, reduce):
+        from . import _native
+
+        loss, dpred, acc = _native.hip_backend().bfocal_forward(pred, target, alpha, gamma, logits, reduce)
+        ctx.save_for_backward(dpred, acc)
+        ctx.reduce = reduce
+        return loss
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy):
+        from . import _native
+
+        dpred, acc = ctx.saved_tensors
+        return _native.hip_backend().bfocal_backward(dpred, acc, gy.contiguous().float(), ctx.reduce), None, None, None, None, None
+
+
+def _fused_rows(pred, target):
+    return pred.is_cuda and pred.dim() == 2 and pred.dtype == torch.float32 and target.dtype == torch.int64 and pred.shape[0] > 0
+
+
+@LOSSES.register_module()
+class BinaryFocalLoss(nn.Module):
+    """misc.py:60-93.  pred (N) -- or any shape, flattened -- against float targets of the same shape (probabilities allowed)."""
+
+    def __init__(self, gamma=2.0, alpha=0.5, logits=True, reduce=True, loss_weight=1.0):
+        super().__init__()
+        assert 0 < alpha < 1
+        self.gamma = gamma
+        self.alpha = alpha
+        self.logits = logits
+        self.reduce = reduce
+        self.loss_weight = loss_weight
+
+    def forward(self, pred, target, **kwargs):
+        if pred.is_cuda and pred.dtype == torch.float32 and pred.numel() > 0 and target.shape == pred.shape:
+            loss = _FusedBinaryFocal.apply(pred.contiguous().view(-1), target.to(torch.float32).contiguous().view(-1), float(self.alpha),
+                                           float(self.gamma), bool(self.logits), bool(self.reduce))
+            if not self.reduce:
+                loss = loss.view(pred.shape)
+        else:
+            loss = binary_focal_loss_reference(pred, target, self.gamma, self.alpha, self.logits, self.reduce)
+        return loss * self.loss_weight
+
+
+@LOSSES.register_module()
+class FocalLoss(nn.Module):
+    """misc.py:97-172.  See the notes above for the all-ignored case, reduction="sum" and bad labels."""
+
+    def __init__(self, gamma=2.0, alpha=0.5, reduction="mean", loss_weight=1.0, ignore_index=-1):
+        super().__init__()
+        assert reduction in ("mean", "sum"), "AssertionError: reduction should be 'mean' or 'sum'"
+        assert isinstance(alpha, (float, list)), "AssertionError: alpha should be of type float"
+        assert isinstance(gamma, float), "AssertionError: gamma should be of type float"
+        assert isinstance(loss_weight, float), "AssertionError: loss_weight should be of type float"
+        assert isinstance(ignore_index, int), "ignore_index must be of type int"
+        self.gamma = gamma
+        self.alpha = alpha
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+        self.ignore_index = ignore_index
+        self._alpha = {}   # (device, C) -> the alpha list as (C) fp32 on the device (_upload_once)
+
+    def forward(self, pred, target, **kwargs):
+        pred, target = _rows_2d(pred, target)
+        if _fused_rows(pred, target):
+            alpha = self.alpha
+            if isinstance(alpha, list):
+                c = pred.shape[1]
+                if len(alpha) != c:
+                    raise ValueError(f"FocalLoss: alpha lists {len(alpha)} classes, the prediction has {c}")
+                alpha = _upload_once(self._alpha, (str(pred.device), c), lambda: torch.tensor(self.alpha, dtype=torch.float32).to(pred.device),
+                                     "FocalLoss(alpha=[...]): the class vector")
+            loss = _FusedFocal.apply(pred, target, alpha, self.gamma, self.reduction, self.ignore_index)
+        else:
+            loss = focal_loss_reference(pred, target, self.gamma, self.alpha, self.reduction, self.ignore_index)
+        return self.loss_weight * loss
+
+
+@LOSSES.register_module()
+class DiceLoss(nn.Module):
+    """misc.py:176-223 (V-Net's Dice loss over the softmax), with the reference's clamp and ignored-class quirks (notes above)."""
+
+    def __init__(self, smooth=1, exponent=2, loss_weight=1.0, ignore_index=-1):
+        super().__init__()
+        self.smooth = smooth
+        self.exponent = exponent
+        self.loss_weight = loss_weight
+        self.ignore_index = ignore_index
+
+    def forward(self, pred, target, **kwargs):
+        pred, target = _rows_2d(pred, target)
+        if _fused_rows(pred, target) and self.exponent > 0:
+            loss = _FusedDice.apply(pred, target.long(), float(self.smooth), float(self.exponent), int(self.ignore_index))
+        else:
+            loss = dice_loss_reference(pred, target.long(), self.smooth, self.exponent, self.ignore_index)
+        return self.loss_weight * loss
