@@ -46,8 +46,9 @@ extern "C" {
  * 10 = pdf_lovasz_workspace_bytes / pdf_lovasz_forward / pdf_lovasz_backward added (no existing parameter list changed);
  * 11 = pdf_openset_metrics_workspace_bytes / pdf_openset_metrics added (no existing parameter list changed);
  * 12 = pdf_scene_bounds / pdf_window_keys_scene added (no existing parameter list changed);
- * 13 = pdf_criteria_workspace_floats / pdf_ce_ex_* / pdf_focal_* / pdf_dice_* / pdf_bfocal_* added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 13
+ * 13 = pdf_criteria_workspace_floats / pdf_ce_ex_* / pdf_focal_* / pdf_dice_* / pdf_bfocal_* added (no existing parameter list changed);
+ * 14 = pdf_grid_pool_* / pdf_grid_unpool_forward / pdf_gva_* added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 14
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -813,6 +814,46 @@ typedef struct PdfCopySeg {
     int src_elems;          /* > 0: number of 4-byte elements of the array src points into (reads of a device-offset window are clamped) */
 } PdfCopySeg;
 int pdf_stage_copy(int nseg, const PdfCopySeg *segs, void *stream);
+
+/* ---- PointTransformer-V2 (point_transformer_v2m2_base.py): partition pooling / unpooling (csrc/grid_pool.hip) and the grouped vector
+ * attention core (csrc/gva.hip).  No float atomics, fixed summation orders, nothing allocated.
+ * pdf_grid_pool_partition (:244-264): key = cell id of voxel_grid(coord - lo[scene], size, start = 0) -- fp32 subtraction, torch's fp32
+ *   floor division, x fastest, scene slowest, extents from the batch-wide maximum -- as int64; stable ascending sort (two 32-bit radix
+ *   sorts) -> cluster (n) int64 = rank of the point's key among the distinct keys, sorted (n) int32 = the sort order (ties in point
+ *   order), idx_ptr int32: n + 1 entries allocated, count[0] + 1 written, count (1) int32 = number of clusters.  xyz (n, 3); ends (scenes)
+ *   int32 ascending scene ends; lo / hi (scenes, 3) from pdf_scene_bounds; workspace: pdf_grid_pool_workspace_bytes(n) bytes, 256-byte
+ *   aligned.  n < 1, n >= 2^31 - 2, size <= 0, a null pointer: PDF_ERR_BAD_ARG before any launch.
+ * pdf_grid_pool_reduce (:265-266): coord_out (m, 3) = segment mean (rows added in ascending sorted position in fp32, one fp32 division);
+ *   feat_out (m, c) = segment max, arg_out (m, c) int32 = the fine row that holds it (first in point order wins a tie).  The coordinate
+ *   pair and the feature triple are each optional (all NULL).
+ * pdf_grid_pool_max_backward: grad_in (n, c)[i, ch] = grad_out[cluster[i], ch] where arg[cluster[i], ch] == i, else 0.
+ * pdf_grid_unpool_forward (:308-309): out (n, c) = x (m, c)[cluster]; its backward is pdf_seg_sum_rows over (idx_ptr, sorted, base 0). */
+long pdf_grid_pool_workspace_bytes(long n);
+int pdf_grid_pool_partition(long n, const float *xyz, const int *ends, int scenes, const float *lo, const float *hi, float size,
+                            long long *cluster, int *sorted, int *idx_ptr, int *count, void *workspace, void *stream);
+int pdf_grid_pool_reduce(long n, long m, int c, const float *xyz, const float *feat, const int *idx_ptr, const int *sorted,
+                         float *coord_out, float *feat_out, int *arg_out, void *stream);
+int pdf_grid_pool_max_backward(long n, long m, int c, const float *grad_out, const long long *cluster, const int *arg, float *grad_in,
+                               void *stream);
+int pdf_grid_unpool_forward(long n, long m, int c, const float *x, const long long *cluster, float *out, void *stream);
+/* Grouped vector attention (:109-129).  idx (n, s) int32 with values in [-1, nk): a negative entry reads a zero key row and is masked
+ * AFTER the softmax (no renormalisation).  inv_off (nk + 1) / inv_entry: the inverse of idx in pdf_seg_sum_rows' table form, base 0.
+ * relation: rel (n, s, c) = (key[idx] - query[n]) * pem + peb, pem / peb (n, s, c) or NULL; backward: g_query = - sum_s g_rel * pem,
+ *   g_key = inverse-segment sums of g_rel * pem, g_pem = g_rel * (key[idx] - query) (each output nullable; g_peb is g_rel itself).
+ * attend (c = 8 * groups, s <= 64: pdf_gva_supported, else PDF_ERR_UNSUPPORTED): p (n, s, groups) = softmax over s of the logits,
+ *   out (n, c)[n, 8 g + j] = sum_s p * [idx >= 0] * (value[idx] + peb); backward: g_logits = p * (m d - sum_t p_t m_t d_t) with
+ *   d = <g_out[n, group], value[idx] + peb>, g_value = inverse-segment sums of p * g_out, g_peb = p * m * g_out (the last two nullable). */
+int pdf_gva_supported(int c, int groups, int s);
+int pdf_gva_relation_forward(long n, long nk, int s, int c, const float *query, const float *key, const int *idx, const float *pem,
+                             const float *peb, float *rel, void *stream);
+int pdf_gva_relation_backward(long n, long nk, int s, int c, const float *g_rel, const float *query, const float *key, const int *idx,
+                              const float *pem, const int *inv_off, const int *inv_entry, float *g_query, float *g_key, float *g_pem,
+                              void *stream);
+int pdf_gva_attend_forward(long n, long nv, int s, int c, int groups, const float *logits, const float *value, const float *peb,
+                           const int *idx, float *out, float *p, void *stream);
+int pdf_gva_attend_backward(long n, long nv, int s, int c, int groups, const float *g_out, const float *p, const float *value,
+                            const float *peb, const int *idx, const int *inv_off, const int *inv_entry, float *g_logits, float *g_value,
+                            float *g_peb, void *stream);
 
 #ifdef __cplusplus
 }

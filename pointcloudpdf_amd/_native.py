@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 13   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 14   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -132,6 +132,15 @@ _HIP_ONLY_PROTOS = {
     "dice_backward": "lipplfppp",
     "bfocal_forward": "lppffiippp",
     "bfocal_backward": "lpppip",
+    # csrc/grid_pool.hip, csrc/gva.hip
+    "grid_pool_partition": "lppippfppppp",
+    "grid_pool_reduce": "llippppppp",
+    "grid_pool_max_backward": "llipppp",
+    "grid_unpool_forward": "llippp",
+    "gva_relation_forward": "lliipppppp",
+    "gva_relation_backward": "llii" + "p" * 10,
+    "gva_attend_forward": "lliii" + "p" * 6,
+    "gva_attend_backward": "lliii" + "p" * 10,
 }
 _KIND = {"i": c_int, "l": c_long, "f": c_float, "d": c_double, "p": c_void_p}
 
@@ -809,6 +818,10 @@ class HipBackend(CBackend):
         lib.pdf_knn_query_grid.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]
         lib.pdf_pt_layer_backward.restype = c_int
         lib.pdf_pt_layer_backward.argtypes = [c_int, c_int, c_int] + [c_void_p] * 19 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p, c_void_p, c_void_p]
+        lib.pdf_grid_pool_workspace_bytes.restype = c_long
+        lib.pdf_grid_pool_workspace_bytes.argtypes = [c_long]
+        lib.pdf_gva_supported.restype = c_int
+        lib.pdf_gva_supported.argtypes = [c_int, c_int, c_int]
         self.fps_mode = os.environ.get("PDFOPS_FPS", "bucketed")  # "bucketed" | "plain"
         self.knn_mode = os.environ.get("PDFOPS_KNN", "grid")      # "grid" | "scan"
         lib.pdf_knn_workspace_bytes.restype = c_long
@@ -2078,6 +2091,106 @@ class HipBackend(CBackend):
         w = self._new(dist2, (n, k), torch.float32)
         self._call("interpolation_weights", n, k, dist2, w)
         return w
+
+    # ---- PointTransformer-V2: partition pooling / unpooling (csrc/grid_pool.hip) ----
+    def grid_pool_partition(self, coord, offset, grid_size, bounds=None):
+        """coord (n, 3) float32, offset (scenes) scene ends -> (cluster (n) int64, sorted (n) int32, idx_ptr (m + 1) int32, m): the
+        partition of point_transformer_v2m2_base.py:248-264.  One host read: the cluster count."""
+        _check(coord, torch.float32, "coord")
+        n = int(coord.shape[0])
+        ends = offset.int().contiguous()
+        lo, hi = bounds if bounds is not None else self.scene_bounds(coord, ends)
+        cluster = torch.empty(n, dtype=torch.int64, device=coord.device)
+        srt = torch.empty(n, dtype=torch.int32, device=coord.device)
+        idx_ptr = torch.empty(n + 1, dtype=torch.int32, device=coord.device)
+        count = torch.empty(1, dtype=torch.int32, device=coord.device)
+        ws = torch.empty(int(self.lib.pdf_grid_pool_workspace_bytes(n)), dtype=torch.uint8, device=coord.device)
+        self._call("grid_pool_partition", n, coord, ends, int(ends.shape[0]), lo.contiguous(), hi.contiguous(), float(grid_size), cluster, srt,
+                   idx_ptr, count, ws)
+        m = int(count.item())
+        return cluster, srt, idx_ptr[:m + 1], m
+
+    def grid_pool_mean(self, coord, idx_ptr, srt):
+        _check(coord, torch.float32, "coord"); _check(idx_ptr, torch.int32, "idx_ptr"); _check(srt, torch.int32, "sorted")
+        m = int(idx_ptr.shape[0]) - 1
+        out = torch.empty((m, 3), dtype=torch.float32, device=coord.device)
+        self._call("grid_pool_reduce", int(coord.shape[0]), m, 0, coord, None, idx_ptr, srt, out, None, None)
+        return out
+
+    def grid_pool_max(self, feat, idx_ptr, srt):
+        _check(feat, torch.float32, "feat"); _check(idx_ptr, torch.int32, "idx_ptr"); _check(srt, torch.int32, "sorted")
+        m, c = int(idx_ptr.shape[0]) - 1, int(feat.shape[1])
+        out = torch.empty((m, c), dtype=torch.float32, device=feat.device)
+        arg = torch.empty((m, c), dtype=torch.int32, device=feat.device)
+        self._call("grid_pool_reduce", int(feat.shape[0]), m, c, None, feat, idx_ptr, srt, None, out, arg)
+        return out, arg
+
+    def grid_pool_max_backward(self, grad_out, cluster, arg):
+        _check(grad_out, torch.float32, "grad_out"); _check(cluster, torch.int64, "cluster"); _check(arg, torch.int32, "arg")
+        n, (m, c) = int(cluster.shape[0]), grad_out.shape
+        out = torch.empty((n, c), dtype=torch.float32, device=grad_out.device)
+        self._call("grid_pool_max_backward", n, int(m), int(c), grad_out, cluster, arg, out)
+        return out
+
+    def grid_unpool_forward(self, x, cluster):
+        _check(x, torch.float32, "x"); _check(cluster, torch.int64, "cluster")
+        n, (m, c) = int(cluster.shape[0]), x.shape
+        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+        self._call("grid_unpool_forward", n, int(m), int(c), x, cluster, out)
+        return out
+
+    def grid_unpool_backward(self, grad_out, idx_ptr, srt):
+        """segmented row sums over (idx_ptr, sorted): pdf_seg_sum_rows' table form with entry_base 0"""
+        _check(grad_out, torch.float32, "grad_out"); _check(idx_ptr, torch.int32, "idx_ptr"); _check(srt, torch.int32, "sorted")
+        m, c = int(idx_ptr.shape[0]) - 1, int(grad_out.shape[1])
+        out = torch.empty((m, c), dtype=torch.float32, device=grad_out.device)
+        self._call("seg_sum_rows", m, c, grad_out, idx_ptr, srt, 0, 1.0, out)
+        return out
+
+    # ---- PointTransformer-V2: grouped vector attention (csrc/gva.hip) ----
+    def gva_supported(self, c, groups, s):
+        return bool(self.lib.pdf_gva_supported(int(c), int(groups), int(s)))
+
+    def gva_relation_forward(self, query, key, idx, pem, peb):
+        n, s = idx.shape
+        c = int(query.shape[1])
+        rel = torch.empty((n, s, c), dtype=torch.float32, device=query.device)
+        self._call("gva_relation_forward", int(n), int(key.shape[0]), int(s), c, query, key, idx, pem, peb, rel)
+        return rel
+
+    def gva_relation_backward(self, g_rel, query, key, idx, pem, need_query, need_key, need_pem):
+        n, s = idx.shape
+        nk, c = int(key.shape[0]), int(query.shape[1])
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=query.device)
+        gq = new(n, c) if need_query else None
+        gk = new(nk, c) if need_key else None
+        gp = new(n, s, c) if need_pem and pem is not None else None
+        off, ent, base = inverse_table(idx, nk) if need_key else (None, None, 0)
+        if base != 0:
+            raise PdfOpsError("gva_relation_backward: inverse table with a non-zero entry base")
+        self._call("gva_relation_backward", int(n), nk, int(s), c, g_rel, query, key, idx, pem, off, ent, gq, gk, gp)
+        return gq, gk, gp
+
+    def gva_attend_forward(self, logits, value, peb, idx):
+        n, s = idx.shape
+        c, groups = int(value.shape[1]), int(logits.shape[2])
+        out = torch.empty((n, c), dtype=torch.float32, device=value.device)
+        p = torch.empty((n, s, groups), dtype=torch.float32, device=value.device)
+        self._call("gva_attend_forward", int(n), int(value.shape[0]), int(s), c, groups, logits, value, peb, idx, out, p)
+        return out, p
+
+    def gva_attend_backward(self, g_out, p, value, peb, idx, need_value, need_peb):
+        n, s = idx.shape
+        nv, c, groups = int(value.shape[0]), int(value.shape[1]), int(p.shape[2])
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=value.device)
+        gl = new(n, s, groups)
+        gv = new(nv, c) if need_value else None
+        gp = new(n, s, c) if need_peb and peb is not None else None
+        off, ent, base = inverse_table(idx, nv) if need_value else (None, None, 0)
+        if base != 0:
+            raise PdfOpsError("gva_attend_backward: inverse table with a non-zero entry base")
+        self._call("gva_attend_backward", int(n), nv, int(s), c, groups, g_out, p, value, peb, idx, off, ent, gl, gv, gp)
+        return gl, gv, gp
 
 
 _lock = threading.Lock()

@@ -28,6 +28,8 @@ EXTRA = {
     "window_edges.hip": ["-ffp-contract=off"],   # the quantised relative positions must round like the torch expression they replace
     "augment.hip": ["-ffp-contract=off"],        # the augmentation must round every product and sum as NumPy's elementwise loops do
     "openset_metrics.hip": ["-ffp-contract=off"],   # the average-precision terms are rounded as written (quotient, quotient, product, sum)
+    "grid_pool.hip": ["-ffp-contract=off"],         # the cell ids and the segment means must round like the torch expressions they replace
+    "gva.hip": ["-ffp-contract=off"],               # the relation (difference, product, sum) is rounded as the torch composition rounds it
 }
 
 

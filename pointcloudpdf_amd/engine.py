@@ -96,7 +96,7 @@ class OpenSegStep(nn.Module):
         ``TrainStep``, ``CapturedStep``, ``FlatGradAllReduce`` and ``testing.OpenSegTester(step, cfg)`` take it as it is."""
         import logging
 
-        from . import stratified  # noqa: F401  (registers ST-v1m1 / ST-v1m1-Recognizer)
+        from . import point_transformer_v2, stratified  # noqa: F401  (register PT-v2m2, ST-v1m1 / ST-v1m1-Recognizer)
 
         log = logging.getLogger(__name__)
         model_cfg, rec_cfg, hook_cfg = _cfg_get(cfg, "model"), _cfg_get(cfg, "recognizer"), _cfg_get(cfg, "model_hooks")

@@ -329,16 +329,21 @@ class SceneTester:
     bit-reproducible and bit-identical to feeding the fragments one at a time through ``FragmentVoter.add``."""
 
     def __init__(self, forward_fn, num_classes, pipeline, fragments_per_batch=4, group=None, prefetch_plan=None, with_segment=False,
-                 device=None, st_backbone=None):
+                 device=None, st_backbone=None, own_geometry=False):
         """``group``: batches per look-ahead pre-pass; default 12, or as many as ``GroupedGeometryLoader.MAX_SCENES`` fragments allow.
         ``st_backbone``: the forward's ``stratified.StratifiedTransformer`` (anything with ``make_geometry`` / ``layers_by_level``): the
         batches then carry ``batch["st_geometry"]`` instead -- FPS chain, neighbour tables and window partitions with one origin per
-        fragment -- from a ``StratifiedPrefetcher(st_backbone, window_origin="scene")`` one group ahead, or inline with ``group=0``."""
+        fragment -- from a ``StratifiedPrefetcher(st_backbone, window_origin="scene")`` one group ahead, or inline with ``group=0``.
+        ``own_geometry``: the forward builds its geometry itself (PT-v2m2): the fragment batches reach it as they are -- no loader, no
+        PT-v1 pre-pass, no ``pdf_geometry`` attached."""
         from . import engine
 
         if st_backbone is not None and not (hasattr(st_backbone, "make_geometry") and hasattr(st_backbone, "layers_by_level")):
             raise TypeError("SceneTester: st_backbone must be a StratifiedTransformer (make_geometry / layers_by_level)")
         self.st_backbone = st_backbone
+        self.own_geometry = bool(own_geometry)
+        if self.own_geometry and st_backbone is not None:
+            raise ValueError("SceneTester: own_geometry and st_backbone exclude each other")
 
         self.forward_fn, self.num_classes, self.pipeline = forward_fn, int(num_classes), pipeline
         self.fragments_per_batch = max(int(fragments_per_batch), 1)
@@ -364,6 +369,8 @@ class SceneTester:
             yield dict(batch, st_geometry=geom.precompute(bb.layers_by_level()))
 
     def _loaded(self, batches):
+        if self.own_geometry:
+            return batches
         if self.st_backbone is not None and (self.device.type != "cuda" or self.group == 0):
             return self._st_inline(batches)
         if self.device.type != "cuda":
@@ -443,15 +450,17 @@ def _cfg_get(cfg, key, default=None):
 
 
 def _st_backbone(model):
-    """The segmentor's backbone when it is a StratifiedTransformer (it builds its own geometry: ``make_geometry``), else None."""
+    """The segmentor's backbone when it is a StratifiedTransformer (window partitions per fragment: ``make_geometry`` /
+    ``layers_by_level``), else None.  (PT-v2m2 has a ``make_geometry`` too; its partition starts at every scene's own minimum, so a batch
+    of fragments is independent forwards: ``SceneTester(own_geometry=True)`` hands the batches to the forward without any pre-pass.)"""
     bb = getattr(model, "backbone", None)
-    return bb if bb is not None and hasattr(bb, "make_geometry") else None
+    return bb if bb is not None and hasattr(bb, "make_geometry") and hasattr(bb, "layers_by_level") else None
 
 
 class _TesterBase:
     """What the two testers share: the scene loop, the result files and the class histograms (test.py:189-266, 572-634)."""
 
-    def __init__(self, cfg, num_classes, forward_fn, with_segment, st_backbone=None):
+    def __init__(self, cfg, num_classes, forward_fn, with_segment, st_backbone=None, own_geometry=False):
         data = _cfg_get(cfg, "data")
         self.cfg = cfg
         self.ignore_index = int(_cfg_get(data, "ignore_index", -1))
@@ -459,7 +468,7 @@ class _TesterBase:
         self.pipeline = TestPipeline(_cfg_get(data, "test"))
         opts = {k: _cfg_get(cfg, k) for k in ("fragments_per_batch", "group", "prefetch_plan") if _cfg_get(cfg, k) is not None}
         self.scene_tester = SceneTester(forward_fn, self.dim_pred, self.pipeline, with_segment=with_segment, device=_cfg_get(cfg, "device"),
-                                        st_backbone=st_backbone, **opts)
+                                        st_backbone=st_backbone, own_geometry=own_geometry, **opts)
 
     def close(self):
         self.scene_tester.close()
@@ -555,7 +564,9 @@ class OpenSegTester(_TesterBase):
             return logits, score.reshape(-1)
 
         data = _cfg_get(cfg, "data")
-        super().__init__(cfg, int(_cfg_get(data, "num_classes")), forward, with_segment=not is_msp, st_backbone=_st_backbone(model))
+        bb = getattr(model, "backbone", None)
+        super().__init__(cfg, int(_cfg_get(data, "num_classes")), forward, with_segment=not is_msp, st_backbone=_st_backbone(model),
+                         own_geometry=hasattr(bb, "make_geometry") and _st_backbone(model) is None)
         self.unknown_label = [int(v) for v in _cfg_get(cfg, "unknown_label", [])]
         self.mask_known = np.ones(self.dim_pred, dtype=bool)
         self.mask_known[self.unknown_label] = False
@@ -621,7 +632,7 @@ class IncrSegTester(_TesterBase):
 
     def __init__(self, step, cfg):
         learner = getattr(step, "learner", step)
-        if isinstance(learner, torch.nn.Module) and any(hasattr(m, "make_geometry") for m in learner.modules()):
+        if isinstance(learner, torch.nn.Module) and any(hasattr(m, "make_geometry") and hasattr(m, "layers_by_level") for m in learner.modules()):
             raise NotImplementedError("IncrSegTester: a StratifiedTransformer learner -- the incremental stage is PointTransformer-V1 only "
                                       "(the reference has no ST incremental recipe); use OpenSegTester for ST-v1m1")
         learner.eval()
