@@ -11,17 +11,27 @@
 // d_fp32(k, s) >= d_bb_fp32 for every point k of the bucket, so a skipped bucket provably has min(d, tmp) == tmp for
 // all its points: pruning is EXACT, no epsilon.  16 buckets form a super-bucket with the same record, checked first.
 //
-// Execution (three kernels, chosen by the size of the largest scene; all give the same indices):
-//   k_fps<K>      one single-wave workgroup per scene, one sample per iteration (small scenes: extra waves only add barriers):
+// Execution (three kernels, chosen by n, the size of the launch's largest scene -- choose() below; all give the same indices):
+//   k_fps         one 4-wave workgroup per scene, one sample per iteration:
 //                 super check (<= 3 per lane) -> bucket check (lanes 0..15) -> 64-lane update of each surviving bucket (one point per
 //                 lane, coalesced 1 KiB loads from the L2-resident sorted copy) -> u64 wave max-reductions;
 //   k_fps_multi   several samples per ROUND, exactly (accepted prefix known before any update, see the kernel header);
 //   k_fps_mw<NW>  the same with one workgroup of NW = 8 / 16 waves per scene: wave 0 selects the round's centres, wave u owns centre u,
-//                 buckets claimed once through LDS and dealt round-robin to the waves (scenes >= 3k / 16k points).
+//                 buckets claimed once through LDS and dealt round-robin to the waves.
+//       n < 768                  k_fps
+//       768 ... 16,383           k_fps_mw<8>
+//       16,384 ... 159,168       k_fps_mw<16>
+//       159,232 ... 181,824      k_fps_multi   (the k_fps_mw records no longer fit the 160 KB of LDS)
+//       181,888 ... 196,608      k_fps         (nor do the 13-word records of k_fps_multi; k_fps keeps 11 words)
+//       above, or n > 2^22       the plain kernel of sampling.hip
+//   (the upper bounds are in steps of one bucket of 64 points).  PDFOPS_FPS_KERNEL = single | multi | mw8 | mw16 forces one of them for
+//   n >= 768 where its records fit (tests and tools/fps_multi_probe.py drive every kernel on one batch with it).
 // A typical sample touches 1-4 buckets instead of 1,563.  Roofline: latency-bound by design; algorithmic HBM bytes 12N + 4M'
 // (SURVEY.md 8d).
 #include "pdfops_common.h"
 #include <stdlib.h>
+#include <string.h>
+#include <type_traits>
 
 extern "C" int pdf_fps_reference_block_log2(int n);
 
@@ -40,6 +50,9 @@ constexpr int FPS_MULTI_MIN = 768;  // smallest largest-scene size for the sever
                                     // candidates bucket by bucket: a 1,562-point scene has 2 super-buckets but 25 buckets)
 constexpr int TWO_MAX_SUPERS = 64;  // k_fps_mw: largest scene (in super-buckets) that takes its candidates in two levels
 constexpr int BKC_MAX = 256;       // k_fps_mw: scenes with at most this many buckets take their round's candidates bucket by bucket
+constexpr int FPS_WAVES = 4;       // waves per scene of k_fps and k_fps_multi
+constexpr int MULTI_K = 8;         // k_fps_multi: most samples per round
+constexpr size_t LDS_LIMIT = 160 * 1024;   // LDS of one workgroup (gfx950); above 64 KB a kernel's limit has to be raised before the launch
 
 struct Layout {  // byte offsets into the caller's workspace
     size_t stats, bbox, hist, cursor, cell, pts, kb, meta, total;
@@ -263,11 +276,17 @@ __global__ __launch_bounds__(64) void k_meta(const float4 *__restrict__ pts, con
     }
 }
 
-// ---------------------------------------------------------------- the sampling kernel (one wave per scene)
-struct Rec {  // SoA record arrays in LDS
+// ---------------------------------------------------------------- bucket and super-bucket records in LDS
+struct Rec {  // SoA record arrays in LDS (k_fps)
     float *lox, *loy, *loz, *hix, *hiy, *hiz, *bx, *by, *bz;
     unsigned *khi, *klo;
 };
+struct Rec2 : Rec {  // the same with the second-best key (k_fps_multi, k_fps_mw: test (a) of k_fps_multi's header)
+    unsigned *k2hi, *k2lo;
+};
+constexpr int REC = 11, REC2 = 13;  // dwords per record
+// entries of one per-wave super-bucket list (a whole number of 64-lane passes, plus one pass of slack)
+__host__ __device__ constexpr int list_stride(int ns_cap) { return ((ns_cap + 63) & ~63) + 64; }
 
 __device__ inline Rec carve(float *base, int n) {
     Rec r;
@@ -277,6 +296,64 @@ __device__ inline Rec carve(float *base, int n) {
     r.khi = reinterpret_cast<unsigned *>(base + 9 * n);
     r.klo = reinterpret_cast<unsigned *>(base + 10 * n);
     return r;
+}
+__device__ inline Rec2 carve2(float *base, int n) {
+    Rec2 r;
+    static_cast<Rec &>(r) = carve(base, n);
+    r.k2hi = reinterpret_cast<unsigned *>(base + 11 * n);
+    r.k2lo = reinterpret_cast<unsigned *>(base + 12 * n);
+    return r;
+}
+
+// The prologue of k_fps and k_fps_multi: the scene's bucket records from k_meta's rows, then the super-bucket records (union of the boxes,
+// best key with its point, for Rec2 the second-best key).  Every thread of the workgroup calls it (two barriers inside; nthreads = the
+// block size).  k_fps_mw writes the same prologue out with its own initialisation in between: see the note at its top.
+template <typename R>
+__device__ __forceinline__ void load_records(const R &B, const R &S, const float *__restrict__ meta, const Scene &sc, int tid, int nthreads) {
+    constexpr bool SECOND = std::is_same<R, Rec2>::value;
+    const int nb = sc.nb, ns = (nb + SUP - 1) / SUP;
+    for (int i = tid; i < nb; i += nthreads) {
+        const float *m = meta + (size_t)(sc.bbase + i) * MSTRIDE;
+        B.lox[i] = m[0]; B.loy[i] = m[1]; B.loz[i] = m[2];
+        B.hix[i] = m[3]; B.hiy[i] = m[4]; B.hiz[i] = m[5];
+        B.khi[i] = __float_as_uint(m[6]); B.klo[i] = __float_as_uint(m[7]);
+        B.bx[i] = m[8]; B.by[i] = m[9]; B.bz[i] = m[10];
+        if constexpr (SECOND) { B.k2hi[i] = __float_as_uint(m[11]); B.k2lo[i] = __float_as_uint(m[12]); }
+    }
+    __syncthreads();
+    for (int s = tid; s < ns; s += nthreads) {
+        float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+        unsigned long long best = 0ull, second = 0ull;
+        int bi = s * SUP;
+        for (int i = s * SUP; i < min(nb, s * SUP + SUP); ++i) {
+            lo[0] = fminf(lo[0], B.lox[i]); lo[1] = fminf(lo[1], B.loy[i]); lo[2] = fminf(lo[2], B.loz[i]);
+            hi[0] = fmaxf(hi[0], B.hix[i]); hi[1] = fmaxf(hi[1], B.hiy[i]); hi[2] = fmaxf(hi[2], B.hiz[i]);
+            const unsigned long long k = ((unsigned long long)B.khi[i] << 32) | B.klo[i];
+            if constexpr (SECOND) {
+                const unsigned long long k2 = ((unsigned long long)B.k2hi[i] << 32) | B.k2lo[i];
+                if (k > best) { second = best > k2 ? best : k2; best = k; bi = i; }
+                else if (k > second) second = k;   // (k2 < k <= best: k2 cannot beat k)
+            } else {
+                if (k > best) { best = k; bi = i; }
+            }
+        }
+        S.lox[s] = lo[0]; S.loy[s] = lo[1]; S.loz[s] = lo[2];
+        S.hix[s] = hi[0]; S.hiy[s] = hi[1]; S.hiz[s] = hi[2];
+        S.khi[s] = (unsigned)(best >> 32); S.klo[s] = (unsigned)best;
+        if constexpr (SECOND) { S.k2hi[s] = (unsigned)(second >> 32); S.k2lo[s] = (unsigned)second; }
+        S.bx[s] = B.bx[bi]; S.by[s] = B.by[bi]; S.bz[s] = B.bz[bi];
+    }
+    __syncthreads();
+}
+
+// the work counters of one scene (pdf_fps_stats_offset): bucket updates | super visits | samples | rounds (k_fps: buckets)
+__device__ __forceinline__ void store_stats(unsigned *__restrict__ stats, unsigned n_updates, unsigned n_supers, int m, unsigned last) {
+    if (threadIdx.x == 0 && stats) {
+        stats[blockIdx.x * 4 + 0] = n_updates;
+        stats[blockIdx.x * 4 + 1] = n_supers;
+        stats[blockIdx.x * 4 + 2] = (unsigned)m;
+        stats[blockIdx.x * 4 + 3] = last;
+    }
 }
 
 // box distance with the operation sequence of dist_as_written (monotone rounding => lower bound of every point's d)
@@ -312,7 +389,7 @@ __device__ __forceinline__ int wave_argmax_key(unsigned hi, unsigned lo, unsigne
 __device__ __forceinline__ float lane_bcast(float v, int lane) {
     return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), lane));
 }
-// single-wave workgroup: LDS traffic only needs the wave's own DS queue drained, never the VMEM queue
+// hand-off between the lanes of ONE wave through LDS: only the wave's own DS queue has to drain, never the VMEM queue
 __device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // Row-wise (16-lane) unsigned max: after the four row_shr folds, lanes 15/31/47/63 hold their row's maximum.
@@ -327,18 +404,15 @@ __device__ __forceinline__ unsigned row_umax_bcast(unsigned v, int row) {
 }
 
 constexpr int FPS_UNROLL = 4;  // bucket loads in flight per wave
-#ifndef PDF_FPS_MW_UNROLL
-#define PDF_FPS_MW_UNROLL 1   // k_fps_mw's update phase is bound by the CU's vector issue (16 waves, ~150 instructions per bucket), not by the
-#endif                        // loads: round 4, levels 100k / 25k / 6250: unroll 1 23.5 / 7.1 / 2.7 ms, 2 24.0 / 7.3 / 2.9, 4 26.6 / 8.6 / 3.1, 8 30.8 / 11.3 / 4.3
 
-// NW waves per scene.  Every wave derives the same sample / active-super / active-bucket lists from the shared LDS
+// FPS_WAVES waves per scene.  Every wave derives the same sample / active-super / active-bucket lists from the shared LDS
 // records (redundantly, no communication); the surviving buckets are dealt round-robin to the waves; two barriers per
 // sample fence the bucket-record writes.
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_fps(const int *__restrict__ offset, const int *__restrict__ new_offset,
-                                                 float4 *__restrict__ pts, const unsigned *__restrict__ kbs,
-                                                 const float *__restrict__ meta, int *__restrict__ idx, int nb_cap,
-                                                 unsigned *__restrict__ stats) {
+__global__ __launch_bounds__(64 * FPS_WAVES) void k_fps(const int *__restrict__ offset, const int *__restrict__ new_offset,
+                                                        float4 *__restrict__ pts, const unsigned *__restrict__ kbs,
+                                                        const float *__restrict__ meta, int *__restrict__ idx, int nb_cap,
+                                                        unsigned *__restrict__ stats) {
+    constexpr int NW = FPS_WAVES;
     extern __shared__ __attribute__((aligned(16))) float fps_lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -349,39 +423,15 @@ __global__ __launch_bounds__(64 * NW) void k_fps(const int *__restrict__ offset,
     const int nb = sc.nb, ns = (nb + SUP - 1) / SUP;
     const int ns_cap = (nb_cap + SUP - 1) / SUP;
     Rec B = carve(fps_lds, nb_cap);
-    Rec S = carve(fps_lds + 11 * nb_cap, ns_cap);
+    Rec S = carve(fps_lds + REC * nb_cap, ns_cap);
     // active-super list, double-buffered by sample parity (a fast wave may already build sample j+1's list while a slow
     // one still refreshes the supers of sample j); active-bucket list (consumed between barriers A and B)
-    unsigned short *slist_base = reinterpret_cast<unsigned short *>(fps_lds + 11 * nb_cap + 11 * ns_cap);
-    const int slist_stride = ((ns_cap + 63) & ~63) + 64;
+    unsigned short *slist_base = reinterpret_cast<unsigned short *>(fps_lds + REC * nb_cap + REC * ns_cap);
+    const int slist_stride = list_stride(ns_cap);
     unsigned short *blist = slist_base + 2 * slist_stride;  // [nb_cap]
     unsigned n_updates = 0, n_supers = 0;
 
-    // load bucket records, build super records
-    for (int i = tid; i < nb; i += 64 * NW) {
-        const float *m = meta + (size_t)(sc.bbase + i) * MSTRIDE;
-        B.lox[i] = m[0]; B.loy[i] = m[1]; B.loz[i] = m[2];
-        B.hix[i] = m[3]; B.hiy[i] = m[4]; B.hiz[i] = m[5];
-        B.khi[i] = __float_as_uint(m[6]); B.klo[i] = __float_as_uint(m[7]);
-        B.bx[i] = m[8]; B.by[i] = m[9]; B.bz[i] = m[10];
-    }
-    __syncthreads();
-    for (int s = tid; s < ns; s += 64 * NW) {
-        float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-        unsigned long long best = 0ull;
-        int bi = s * SUP;
-        for (int i = s * SUP; i < min(nb, s * SUP + SUP); ++i) {
-            lo[0] = fminf(lo[0], B.lox[i]); lo[1] = fminf(lo[1], B.loy[i]); lo[2] = fminf(lo[2], B.loz[i]);
-            hi[0] = fmaxf(hi[0], B.hix[i]); hi[1] = fmaxf(hi[1], B.hiy[i]); hi[2] = fmaxf(hi[2], B.hiz[i]);
-            const unsigned long long k = ((unsigned long long)B.khi[i] << 32) | B.klo[i];
-            if (k > best) { best = k; bi = i; }
-        }
-        S.lox[s] = lo[0]; S.loy[s] = lo[1]; S.loz[s] = lo[2];
-        S.hix[s] = hi[0]; S.hiy[s] = hi[1]; S.hiz[s] = hi[2];
-        S.khi[s] = (unsigned)(best >> 32); S.klo[s] = (unsigned)best;
-        S.bx[s] = B.bx[bi]; S.by[s] = B.by[bi]; S.bz[s] = B.bz[bi];
-    }
-    __syncthreads();
+    load_records(B, S, meta, sc, tid, 64 * NW);
 
     if (tid == 0) idx[sc.start_m] = sc.start_n;
     // sample 1 needs no update pass: tmp already holds the distances to sample 0 (k_scatter)
@@ -427,7 +477,7 @@ __global__ __launch_bounds__(64 * NW) void k_fps(const int *__restrict__ offset,
         }
         n_supers += n_sup;
         n_updates += n_bk;
-        if (NW > 1) __syncthreads(); else lds_fence();  // A: nobody still reads bucket records / every list is complete
+        __syncthreads();  // A: nobody still reads bucket records / every list is complete
 
         // ---- 4. update the surviving buckets (dealt round-robin to the waves, FPS_UNROLL loads in flight)
         for (int i0 = wave * FPS_UNROLL; i0 < n_bk; i0 += NW * FPS_UNROLL) {
@@ -464,7 +514,7 @@ __global__ __launch_bounds__(64 * NW) void k_fps(const int *__restrict__ offset,
                 }
             }
         }
-        if (NW > 1) __syncthreads(); else lds_fence();  // B: bucket records + tmp stores of every wave are visible
+        __syncthreads();  // B: bucket records + tmp stores of every wave are visible
 
         // ---- 5. refresh the touched super records (every wave, redundantly; 4 supers per pass, one per 16-lane row)
         for (int g = 0; g < n_sup; g += 4) {
@@ -487,12 +537,12 @@ __global__ __launch_bounds__(64 * NW) void k_fps(const int *__restrict__ offset,
         }
         lds_fence();
     }
-    if (tid == 0 && stats) {
-        stats[blockIdx.x * 4 + 0] = n_updates;
-        stats[blockIdx.x * 4 + 1] = n_supers;
-        stats[blockIdx.x * 4 + 2] = (unsigned)sc.m;
-        stats[blockIdx.x * 4 + 3] = (unsigned)nb;
-    }
+    store_stats(stats, n_updates, n_supers, sc.m, (unsigned)nb);
+}
+
+// dynamic LDS of k_fps, as carved at its top: bucket and super records, the two active-super lists, the active-bucket list
+size_t lds_single(int nb_cap, int ns_cap) {
+    return (size_t)(REC * (nb_cap + ns_cap)) * 4 + (size_t)(2 * list_stride(ns_cap) + nb_cap + 64) * 2;
 }
 
 // ---------------------------------------------------------------- several samples per round (exact)
@@ -507,23 +557,7 @@ __global__ __launch_bounds__(64 * NW) void k_fps(const int *__restrict__ offset,
 // tmp = 0.  Keys are unique (the low word carries the point's index), so c_t is the unique arg-max after t-1 insertions.
 // Both tests use values from before the round, the accepted prefix is known before any update, and the updates
 // tmp = min(tmp, d(., c_u)) commute -- one pass over the union of the touched buckets applies them all.
-// Records carry the second-best key per bucket and per super-bucket for (a).
-struct Rec2 {
-    float *lox, *loy, *loz, *hix, *hiy, *hiz, *bx, *by, *bz;
-    unsigned *khi, *klo, *k2hi, *k2lo;
-};
-constexpr int REC2 = 13;
-__device__ inline Rec2 carve2(float *base, int n) {
-    Rec2 r;
-    r.lox = base; r.loy = base + n; r.loz = base + 2 * n;
-    r.hix = base + 3 * n; r.hiy = base + 4 * n; r.hiz = base + 5 * n;
-    r.bx = base + 6 * n; r.by = base + 7 * n; r.bz = base + 8 * n;
-    r.khi = reinterpret_cast<unsigned *>(base + 9 * n);
-    r.klo = reinterpret_cast<unsigned *>(base + 10 * n);
-    r.k2hi = reinterpret_cast<unsigned *>(base + 11 * n);
-    r.k2lo = reinterpret_cast<unsigned *>(base + 12 * n);
-    return r;
-}
+// Records carry the second-best key per bucket and per super-bucket for (a): Rec2.
 __device__ __forceinline__ float box_dist_v(float lox, float loy, float loz, float hix, float hiy, float hiz, float cx, float cy, float cz) {
     const float gx = fmaxf(fmaxf(lox - cx, cx - hix), 0.f);
     const float gy = fmaxf(fmaxf(loy - cy, cy - hiy), 0.f);
@@ -532,11 +566,11 @@ __device__ __forceinline__ float box_dist_v(float lox, float loy, float loz, flo
 }
 __device__ __forceinline__ bool key_gt(unsigned ah, unsigned al, unsigned bh, unsigned bl) { return ah > bh || (ah == bh && al > bl); }
 
-template <int NW, int KMAX>
-__global__ __launch_bounds__(64 * NW) void k_fps_multi(const int *__restrict__ offset, const int *__restrict__ new_offset,
-                                                       float4 *__restrict__ pts, const unsigned *__restrict__ kbs,
-                                                       const float *__restrict__ meta, int *__restrict__ idx, int nb_cap,
-                                                       unsigned *__restrict__ stats) {
+__global__ __launch_bounds__(64 * FPS_WAVES) void k_fps_multi(const int *__restrict__ offset, const int *__restrict__ new_offset,
+                                                              float4 *__restrict__ pts, const unsigned *__restrict__ kbs,
+                                                              const float *__restrict__ meta, int *__restrict__ idx, int nb_cap,
+                                                              unsigned *__restrict__ stats) {
+    constexpr int NW = FPS_WAVES, KMAX = MULTI_K;
     extern __shared__ __attribute__((aligned(16))) float fps_lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -549,48 +583,14 @@ __global__ __launch_bounds__(64 * NW) void k_fps_multi(const int *__restrict__ o
     Rec2 B = carve2(fps_lds, nb_cap);
     Rec2 S = carve2(fps_lds + REC2 * nb_cap, ns_cap);
     unsigned short *slist_base = reinterpret_cast<unsigned short *>(fps_lds + REC2 * nb_cap + REC2 * ns_cap);
-    const int slist_stride = ((ns_cap + 63) & ~63) + 64;
+    const int slist_stride = list_stride(ns_cap);
     unsigned short *blist = slist_base + 2 * slist_stride;  // [nb_cap]
     unsigned n_updates = 0, n_supers = 0, n_rounds = 0;
-#ifdef FPS_PROFILE
-    unsigned long long tc[5] = {0, 0, 0, 0, 0}, t_prev = __builtin_readcyclecounter();
-#define FPS_TICK(i_) do { const unsigned long long t_now = __builtin_readcyclecounter(); tc[i_] += t_now - t_prev; t_prev = t_now; } while (0)
-#else
-#define FPS_TICK(i_) do {} while (0)
-#endif
 
-    for (int i = tid; i < nb; i += 64 * NW) {
-        const float *m = meta + (size_t)(sc.bbase + i) * MSTRIDE;
-        B.lox[i] = m[0]; B.loy[i] = m[1]; B.loz[i] = m[2];
-        B.hix[i] = m[3]; B.hiy[i] = m[4]; B.hiz[i] = m[5];
-        B.khi[i] = __float_as_uint(m[6]); B.klo[i] = __float_as_uint(m[7]);
-        B.bx[i] = m[8]; B.by[i] = m[9]; B.bz[i] = m[10];
-        B.k2hi[i] = __float_as_uint(m[11]); B.k2lo[i] = __float_as_uint(m[12]);
-    }
-    __syncthreads();
-    for (int s = tid; s < ns; s += 64 * NW) {
-        float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-        unsigned long long best = 0ull, second = 0ull;
-        int bi = s * SUP;
-        for (int i = s * SUP; i < min(nb, s * SUP + SUP); ++i) {
-            lo[0] = fminf(lo[0], B.lox[i]); lo[1] = fminf(lo[1], B.loy[i]); lo[2] = fminf(lo[2], B.loz[i]);
-            hi[0] = fmaxf(hi[0], B.hix[i]); hi[1] = fmaxf(hi[1], B.hiy[i]); hi[2] = fmaxf(hi[2], B.hiz[i]);
-            const unsigned long long k = ((unsigned long long)B.khi[i] << 32) | B.klo[i];
-            const unsigned long long k2 = ((unsigned long long)B.k2hi[i] << 32) | B.k2lo[i];
-            if (k > best) { second = best > k2 ? best : k2; best = k; bi = i; }
-            else if (k > second) second = k;   // (k2 < k <= best: k2 cannot beat k)
-        }
-        S.lox[s] = lo[0]; S.loy[s] = lo[1]; S.loz[s] = lo[2];
-        S.hix[s] = hi[0]; S.hiy[s] = hi[1]; S.hiz[s] = hi[2];
-        S.khi[s] = (unsigned)(best >> 32); S.klo[s] = (unsigned)best;
-        S.k2hi[s] = (unsigned)(second >> 32); S.k2lo[s] = (unsigned)second;
-        S.bx[s] = B.bx[bi]; S.by[s] = B.by[bi]; S.bz[s] = B.bz[bi];
-    }
-    __syncthreads();
+    load_records(B, S, meta, sc, tid, 64 * NW);
 
     if (tid == 0) idx[sc.start_m] = sc.start_n;
     int j = 1;
-    FPS_TICK(4);
     while (j < sc.m) {
         // ---- 1. candidates (every wave, redundantly): per-lane best over its supers, then up to KMAX wave arg-maxes
         float cx[KMAX], cy[KMAX], cz[KMAX];
@@ -637,7 +637,6 @@ __global__ __launch_bounds__(64 * NW) void k_fps_multi(const int *__restrict__ o
         j += a;
         ++n_rounds;
         if (j >= sc.m) break;  // the last sample needs no distance update
-        FPS_TICK(0);
 
         // ---- 2. active supers (touched by any accepted centre) -> slist
         unsigned short *slist = slist_base + (n_rounds & 1) * slist_stride;
@@ -678,8 +677,7 @@ __global__ __launch_bounds__(64 * NW) void k_fps_multi(const int *__restrict__ o
         }
         n_supers += n_sup;
         n_updates += n_bk;
-        if (NW > 1) __syncthreads(); else lds_fence();  // A
-        FPS_TICK(1);
+        __syncthreads();  // A
 
         // ---- 4. update the surviving buckets with every accepted centre
         for (int i0 = wave * FPS_UNROLL; i0 < n_bk; i0 += NW * FPS_UNROLL) {
@@ -723,8 +721,7 @@ __global__ __launch_bounds__(64 * NW) void k_fps_multi(const int *__restrict__ o
                 }
             }
         }
-        if (NW > 1) __syncthreads(); else lds_fence();  // B
-        FPS_TICK(2);
+        __syncthreads();  // B
 
         // ---- 5. refresh the touched super records (best + second-best; 4 supers per pass, one per 16-lane row)
         for (int g = 0; g < n_sup; g += 4) {
@@ -751,21 +748,16 @@ __global__ __launch_bounds__(64 * NW) void k_fps_multi(const int *__restrict__ o
             }
         }
         lds_fence();
-        FPS_TICK(3);
     }
-    if (tid == 0 && stats) {
-        stats[blockIdx.x * 4 + 0] = n_updates;
-        stats[blockIdx.x * 4 + 1] = n_supers;
-        stats[blockIdx.x * 4 + 2] = (unsigned)sc.m;
-        stats[blockIdx.x * 4 + 3] = n_rounds;
-#ifdef FPS_PROFILE
-        for (int i = 0; i < 4; ++i) stats[blockIdx.x * 4 + i] = (unsigned)(tc[i] >> 10);   // kilo-cycles: candidates | lists | updates | refresh
-#endif
-    }
-#undef FPS_TICK
+    store_stats(stats, n_updates, n_supers, sc.m, n_rounds);
 }
 
-// k_fps_mw, RANK: for every unit (super-bucket or bucket) the units of this wave's slice with a greater key, added to rank[] in LDS; then
+// dynamic LDS of k_fps_multi: the layout of k_fps with the larger records
+size_t lds_multi(int nb_cap, int ns_cap) {
+    return (size_t)(REC2 * (nb_cap + ns_cap)) * 4 + (size_t)(2 * list_stride(ns_cap) + nb_cap + 64) * 2;
+}
+
+// k_fps_mw: for every unit (super-bucket or bucket) the units of this wave's slice with a greater key, added to rank[] in LDS; then
 // (wave 0, after a barrier) the units of rank < KMAX placed best first into cand[].  N: units per lane.
 template <int N, int NW>
 __device__ __forceinline__ void rank_count(const Rec2 &U, int nu, unsigned *rank, int lane, int wave) {
@@ -813,13 +805,16 @@ __device__ __forceinline__ void rank_place(const Rec2 &U, int nu, unsigned *rank
 //            claim word (the owner clears the word).
 //   barrier B
 //   phase 4  the shared super list is dealt to the waves (4 supers per pass); barrier C.
-template <int NW, bool RANK>
+// This kernel runs at the limit of 106 SGPRs with spills to VGPR lanes, and its round time follows the register allocation: with
+// `two_level` folded to its only value (1) or the prologue taken from load_records(), the round loop reloads more spilled SGPRs and the
+// level-1 launch (100k points) takes 22.6-22.8 ms instead of 22.5 (profiles/fps_refactor_check.json).  So the argument and the
+// written-out prologue stay until the loop's SGPR pressure is lowered; the host always passes two_level = 1.
+template <int NW>
 __global__ __launch_bounds__(64 * NW) void k_fps_mw(const int *__restrict__ offset, const int *__restrict__ new_offset,
                                                     float4 *__restrict__ pts, const unsigned *__restrict__ kbs,
                                                     const float *__restrict__ meta, int *__restrict__ idx, int nb_cap,
                                                     unsigned *__restrict__ stats, int two_level) {
     constexpr int KMAX = NW;
-    constexpr int UNR = PDF_FPS_MW_UNROLL;   // bucket loads in flight per wave
     constexpr int NSL = (NS_MAX + 63) / 64;   // supers per lane
     extern __shared__ __attribute__((aligned(16))) float fps_lds[];
     const int tid = threadIdx.x;
@@ -838,22 +833,17 @@ __global__ __launch_bounds__(64 * NW) void k_fps_mw(const int *__restrict__ offs
     float *cent = reinterpret_cast<float *>(cnt + 4);                                            // [3 * 16] the round's centres
     int *cent_n = reinterpret_cast<int *>(cent + 3 * 16);                                      // [4]
     const int nr_cap = nb_cap <= BKC_MAX ? nb_cap : ns_cap;
-    unsigned *rank = reinterpret_cast<unsigned *>(cent_n + 4);                                   // [nr_cap] units with a greater key (RANK)
+    unsigned *rank = reinterpret_cast<unsigned *>(cent_n + 4);                                   // [nr_cap] units with a greater key
     int *cand = reinterpret_cast<int *>(rank + nr_cap);                                          // [16] the round's candidate units, best first
     unsigned *c_s2h = reinterpret_cast<unsigned *>(cand + 16), *c_s2l = c_s2h + 16;              // [16] [16] their supers' second-best keys
     unsigned *rank2 = c_s2l + 16;                                                                // [16 * SUP] buckets of the best supers with a greater key
     unsigned short *blist = reinterpret_cast<unsigned short *>(rank2 + 16 * SUP);                // [nb_cap + 64] shared
     unsigned short *slist = blist + nb_cap + 64;                                                 // [ns_cap + 64] shared
-    const int psl_stride = ((ns_cap + 63) & ~63) + 64;
+    const int psl_stride = list_stride(ns_cap);
     unsigned short *pslist = slist + ns_cap + 64 + wave * psl_stride;                            // private per wave
     unsigned n_updates = 0, n_supers = 0, n_rounds = 0;
-#ifdef FPS_PROFILE
-    unsigned long long tc[5] = {0, 0, 0, 0, 0}, t_prev = __builtin_readcyclecounter();
-#define FPS_TICK(i_) do { const unsigned long long t_now = __builtin_readcyclecounter(); tc[i_] += t_now - t_prev; t_prev = t_now; } while (0)
-#else
-#define FPS_TICK(i_) do {} while (0)
-#endif
 
+    // (load_records() for Rec2, with this kernel's claim words, counters and rank arrays cleared on the way)
     for (int i = tid; i < nb; i += 64 * NW) {
         const float *m = meta + (size_t)(sc.bbase + i) * MSTRIDE;
         B.lox[i] = m[0]; B.loy[i] = m[1]; B.loz[i] = m[2];
@@ -891,156 +881,108 @@ __global__ __launch_bounds__(64 * NW) void k_fps_mw(const int *__restrict__ offs
 
     if (tid == 0) idx[sc.start_m] = sc.start_n;
     int j = 1;
-    FPS_TICK(4);
     while (j < sc.m) {
         // ---- 1. candidates.  The round's candidates are the KMAX supers with the largest best keys, best first (c_t = the best point
         // outside the supers of c_1..c_{t-1}); tests (a) and (b) of k_fps_multi only use values from before the round, so the accepted
-        // prefix is the first t that fails either.  Rounds 2-3 found the candidates one wave arg-max after the other in wave 0 (~1,450
-        // cycles each, 16k of the 31k cycles of a level-1 round).  RANK: every wave counts, for every super, the supers of ITS slice with a
-        // greater key (broadcast LDS reads, LDS adds); after barrier R wave 0 places the supers of rank < KMAX, lane t takes candidate t
-        // and all tests run at once.
-        if (RANK) {
-            // The candidate UNITS: super-buckets (1,024 points) at level 1; the buckets themselves (64 points) when the scene has at most
-            // BKC_MAX of them (levels 2+) -- a scene of 25k points has 25 supers, one of 6,250 has 7, which capped a round at that many
-            // centres and let test (a) (second-best key of a 1,024-point unit) end it earlier still.  The proof of k_fps_multi holds for any
-            // partition into units that carry their best and second-best key.
-            const bool bkc = nb_cap <= BKC_MAX;   // (by the launch's largest scene: the rank array is sized for it; either way the same samples)
-            // Larger scenes, two levels: the KMAX best buckets lie inside the KMAX best super-buckets (a super whose best key is below the
-            // KMAX-th best bucket key holds none of them), so rank the supers, then the <= KMAX * SUP buckets of the KMAX best supers.
-            // (measured: 25k-point scenes 7.2 -> 5.5 ms; 100k-point scenes 22.5 -> 23.3 -- with 98 supers the two extra barriers cost more than
-            // the better yield returns: only up to TWO_MAX_SUPERS supers)
-            const bool two = !bkc && two_level && ns_cap <= TWO_MAX_SUPERS;
-            const Rec2 &U_ = (bkc || two) ? B : S;
-            const int nu = bkc ? nb : ns;
-            if (bkc) rank_count<BKC_MAX / 64, NW>(B, nu, rank, lane, wave); else rank_count<NSL, NW>(S, nu, rank, lane, wave);
-            __syncthreads();  // R: ranks complete
-            if (two) {
-                if (wave == 0) rank_place<NSL, KMAX>(S, ns, rank, cand, lane);
-                __syncthreads();  // R2: the KMAX best supers are listed
-                constexpr int NSLOT = KMAX * SUP, NQ = NSLOT / 64, JS = NSLOT / NW;
-                unsigned long long mykey[NQ];
-                unsigned above[NQ];
+        // prefix is the first t that fails either.  Every wave counts, for every super, the supers of ITS slice with a greater key
+        // (broadcast LDS reads, LDS adds); after barrier R wave 0 places the supers of rank < KMAX, lane t takes candidate t and all
+        // tests run at once.  (One wave arg-max after the other in wave 0 cost ~1,450 cycles per candidate, 16k of the 31k cycles of a
+        // level-1 round: profiles/r04_fps_rank_ab.txt.)
+        // The candidate UNITS: super-buckets (1,024 points) at level 1; the buckets themselves (64 points) when the scene has at most
+        // BKC_MAX of them (levels 2+) -- a scene of 25k points has 25 supers, one of 6,250 has 7, which capped a round at that many
+        // centres and let test (a) (second-best key of a 1,024-point unit) end it earlier still.  The proof of k_fps_multi holds for any
+        // partition into units that carry their best and second-best key.
+        const bool bkc = nb_cap <= BKC_MAX;   // (by the launch's largest scene: the rank array is sized for it; either way the same samples)
+        // Larger scenes, two levels: the KMAX best buckets lie inside the KMAX best super-buckets (a super whose best key is below the
+        // KMAX-th best bucket key holds none of them), so rank the supers, then the <= KMAX * SUP buckets of the KMAX best supers.
+        // (measured: 25k-point scenes 7.2 -> 5.5 ms; 100k-point scenes 22.5 -> 23.3 -- with 98 supers the two extra barriers cost more than
+        // the better yield returns: only up to TWO_MAX_SUPERS supers)
+        const bool two = !bkc && two_level && ns_cap <= TWO_MAX_SUPERS;
+        const Rec2 &U_ = (bkc || two) ? B : S;
+        const int nu = bkc ? nb : ns;
+        if (bkc) rank_count<BKC_MAX / 64, NW>(B, nu, rank, lane, wave); else rank_count<NSL, NW>(S, nu, rank, lane, wave);
+        __syncthreads();  // R: ranks complete
+        if (two) {
+            if (wave == 0) rank_place<NSL, KMAX>(S, ns, rank, cand, lane);
+            __syncthreads();  // R2: the KMAX best supers are listed
+            constexpr int NSLOT = KMAX * SUP, NQ = NSLOT / 64, JS = NSLOT / NW;
+            unsigned long long mykey[NQ];
+            unsigned above[NQ];
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                const int q = lane + 64 * i, sup = cand[q / SUP], bk = sup * SUP + q % SUP;
+                mykey[i] = (sup >= 0 && bk < nb) ? (((unsigned long long)B.khi[bk] << 32) | B.klo[bk]) : 0ull;
+                above[i] = 0u;
+            }
+            for (int q = wave * JS; q < wave * JS + JS; ++q) {
+                const int sup = cand[q / SUP], bk = sup * SUP + q % SUP;
+                const unsigned long long kj = (sup >= 0 && bk < nb) ? (((unsigned long long)B.khi[bk] << 32) | B.klo[bk]) : 0ull;
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) above[i] += kj > mykey[i] ? 1u : 0u;
+            }
+#pragma unroll
+            for (int i = 0; i < NQ; ++i)
+                if (above[i]) atomicAdd(&rank2[lane + 64 * i], above[i]);
+            __syncthreads();  // R3: bucket ranks complete
+            if (wave == 0) {
+                int mybk[NQ];
 #pragma unroll
                 for (int i = 0; i < NQ; ++i) {
-                    const int q = lane + 64 * i, sup = cand[q / SUP], bk = sup * SUP + q % SUP;
-                    mykey[i] = (sup >= 0 && bk < nb) ? (((unsigned long long)B.khi[bk] << 32) | B.klo[bk]) : 0ull;
-                    above[i] = 0u;
-                }
-                for (int q = wave * JS; q < wave * JS + JS; ++q) {
-                    const int sup = cand[q / SUP], bk = sup * SUP + q % SUP;
-                    const unsigned long long kj = (sup >= 0 && bk < nb) ? (((unsigned long long)B.khi[bk] << 32) | B.klo[bk]) : 0ull;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i) above[i] += kj > mykey[i] ? 1u : 0u;
-                }
-#pragma unroll
-                for (int i = 0; i < NQ; ++i)
-                    if (above[i]) atomicAdd(&rank2[lane + 64 * i], above[i]);
-                __syncthreads();  // R3: bucket ranks complete
-                if (wave == 0) {
-                    int mybk[NQ];
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i) {
-                        const int q = lane + 64 * i, sup = cand[q / SUP];
-                        mybk[i] = sup >= 0 && sup * SUP + q % SUP < nb ? sup * SUP + q % SUP : -1;
-                    }
-                    lds_fence();
-                    if (lane < 16) cand[lane] = -1;
-                    lds_fence();
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i) {
-                        const unsigned rk = rank2[lane + 64 * i];
-                        rank2[lane + 64 * i] = 0u;
-                        if (mybk[i] >= 0 && rk < (unsigned)KMAX && (B.khi[mybk[i]] | B.klo[mybk[i]]) != 0u) cand[rk] = mybk[i];
-                    }
-                }
-            }
-            if (wave == 0) {
-                constexpr int G = 64 / KMAX;          // lane groups of test (b): lane = (g, t)
-                const int kmax = min(KMAX, sc.m - j);
-                if (!two) { if (bkc) rank_place<BKC_MAX / 64, KMAX>(B, nu, rank, cand, lane); else rank_place<NSL, KMAX>(S, nu, rank, cand, lane); }
-                lds_fence();
-                const int t = lane % KMAX, g = lane / KMAX;
-                const int cs = cand[t];
-                const bool valid = cs >= 0 && t < kmax;
-                const int c0 = cs >= 0 ? cs : 0;
-                const unsigned kh = U_.khi[c0], kl = U_.klo[c0];
-                const float x = U_.bx[c0], y = U_.by[c0], z = U_.bz[c0];
-                if (lane < KMAX) {
-                    cent[3 * t + 0] = x; cent[3 * t + 1] = y; cent[3 * t + 2] = z;
-                    c_s2h[t] = valid ? U_.k2hi[c0] : 0u; c_s2l[t] = valid ? U_.k2lo[c0] : 0u;
+                    const int q = lane + 64 * i, sup = cand[q / SUP];
+                    mybk[i] = sup >= 0 && sup * SUP + q % SUP < nb ? sup * SUP + q % SUP : -1;
                 }
                 lds_fence();
-                bool fail = !valid;
-                {   // (a) the key beats the second-best key of every earlier candidate's super
-                    unsigned long long bound = 0ull;
-#pragma unroll
-                    for (int u = 0; u < KMAX - 1; ++u) {
-                        const unsigned long long k2 = ((unsigned long long)c_s2h[u] << 32) | c_s2l[u];
-                        if (u < t && k2 > bound) bound = k2;
-                    }
-                    const unsigned long long key = ((unsigned long long)kh << 32) | kl;
-                    fail = fail || (t > 0 && !(key > bound));
-                }
-#pragma unroll
-                for (int uu = 0; uu < KMAX / G; ++uu) {   // (b) no earlier candidate lowers tmp of this one
-                    const int u = g + G * uu;
-                    const bool near = pdf_f32_ordered(dist_as_written(x, y, z, cent[3 * u + 0], cent[3 * u + 1], cent[3 * u + 2])) < kh;
-                    fail = fail || (u < t && near);
-                }
-                unsigned long long fm = __ballot(fail);
-#pragma unroll
-                for (int sft = KMAX; sft < 64; sft <<= 1) fm |= fm >> sft;
-                const unsigned f = (unsigned)fm & ((1u << KMAX) - 1u) & ~1u;       // (candidate 0 is always accepted)
-                const int acc = f ? __ffs(f) - 1 : KMAX;
-                if (lane < acc) idx[sc.start_m + j + lane] = sc.start_n + (int)(~kl & REL_MASK);
-                if (lane == 0) cent_n[0] = acc;
                 if (lane < 16) cand[lane] = -1;
-            }
-        } else
-        // (rounds 2-3) WAVE 0 ONLY, one candidate after the other: each lane keeps the records of ITS supers (s = lane + 64 i) in
-        // registers for the round; lane u holds accepted centre u, so test (b) is one distance per lane.
-        if (wave == 0) {
-            unsigned skh[NSL], skl[NSL], sk2h[NSL], sk2l[NSL];
-            float sbx[NSL], sby[NSL], sbz[NSL];
+                lds_fence();
 #pragma unroll
-            for (int i = 0; i < NSL; ++i) {
-                const int s = lane + 64 * i;
-                const bool ok = s < ns;
-                skh[i] = ok ? S.khi[s] : 0u; skl[i] = ok ? S.klo[s] : 0u;
-                sk2h[i] = ok ? S.k2hi[s] : 0u; sk2l[i] = ok ? S.k2lo[s] : 0u;
-                sbx[i] = ok ? S.bx[s] : 0.f; sby[i] = ok ? S.by[s] : 0.f; sbz[i] = ok ? S.bz[s] : 0.f;
-            }
-            const int kmax = min(KMAX, sc.m - j);
-            int acc = 0, my_idx = 0;
-            float mcx = 0.f, mcy = 0.f, mcz = 0.f;   // lane u: centre u
-            unsigned bound_hi = 0u, bound_lo = 0u;
-            for (int t = 0; t < kmax; ++t) {
-                unsigned bhi = skh[0], blo = skl[0], b2h = sk2h[0], b2l = sk2l[0];
-                float bx = sbx[0], by = sby[0], bz = sbz[0];
-                int bi = 0;
-#pragma unroll
-                for (int i = 1; i < NSL; ++i)
-                    if (key_gt(skh[i], skl[i], bhi, blo)) { bhi = skh[i]; blo = skl[i]; b2h = sk2h[i]; b2l = sk2l[i]; bx = sbx[i]; by = sby[i]; bz = sbz[i]; bi = i; }
-                unsigned whi, wlo;
-                const int wl = wave_argmax_key(bhi, blo, whi, wlo);
-                if (t > 0 && !key_gt(whi, wlo, bound_hi, bound_lo)) break;          // (a)  (also stops at key 0: nothing left)
-                const float x = lane_bcast(bx, wl), y = lane_bcast(by, wl), z = lane_bcast(bz, wl);
-                const bool near = lane < t && pdf_f32_ordered(dist_as_written(x, y, z, mcx, mcy, mcz)) < whi;   // (b)
-                if (__ballot(near) != 0ull) break;
-                const unsigned s2h = (unsigned)__builtin_amdgcn_readlane((int)b2h, wl), s2l = (unsigned)__builtin_amdgcn_readlane((int)b2l, wl);
-                if (lane == t) { mcx = x; mcy = y; mcz = z; my_idx = sc.start_n + (int)(~wlo & REL_MASK); }
-                acc = t + 1;
-                if (key_gt(s2h, s2l, bound_hi, bound_lo)) { bound_hi = s2h; bound_lo = s2l; }
-                if (lane == wl) {   // retire the taken super from this lane's slots
-#pragma unroll
-                    for (int i = 0; i < NSL; ++i) if (i == bi) { skh[i] = 0u; skl[i] = 0u; }
+                for (int i = 0; i < NQ; ++i) {
+                    const unsigned rk = rank2[lane + 64 * i];
+                    rank2[lane + 64 * i] = 0u;
+                    if (mybk[i] >= 0 && rk < (unsigned)KMAX && (B.khi[mybk[i]] | B.klo[mybk[i]]) != 0u) cand[rk] = mybk[i];
                 }
             }
-            if (lane < acc) {
-                idx[sc.start_m + j + lane] = my_idx;
-                cent[3 * lane + 0] = mcx; cent[3 * lane + 1] = mcy; cent[3 * lane + 2] = mcz;
+        }
+        if (wave == 0) {
+            constexpr int G = 64 / KMAX;          // lane groups of test (b): lane = (g, t)
+            const int kmax = min(KMAX, sc.m - j);
+            if (!two) { if (bkc) rank_place<BKC_MAX / 64, KMAX>(B, nu, rank, cand, lane); else rank_place<NSL, KMAX>(S, nu, rank, cand, lane); }
+            lds_fence();
+            const int t = lane % KMAX, g = lane / KMAX;
+            const int cs = cand[t];
+            const bool valid = cs >= 0 && t < kmax;
+            const int c0 = cs >= 0 ? cs : 0;
+            const unsigned kh = U_.khi[c0], kl = U_.klo[c0];
+            const float x = U_.bx[c0], y = U_.by[c0], z = U_.bz[c0];
+            if (lane < KMAX) {
+                cent[3 * t + 0] = x; cent[3 * t + 1] = y; cent[3 * t + 2] = z;
+                c_s2h[t] = valid ? U_.k2hi[c0] : 0u; c_s2l[t] = valid ? U_.k2lo[c0] : 0u;
             }
+            lds_fence();
+            bool fail = !valid;
+            {   // (a) the key beats the second-best key of every earlier candidate's super
+                unsigned long long bound = 0ull;
+#pragma unroll
+                for (int u = 0; u < KMAX - 1; ++u) {
+                    const unsigned long long k2 = ((unsigned long long)c_s2h[u] << 32) | c_s2l[u];
+                    if (u < t && k2 > bound) bound = k2;
+                }
+                const unsigned long long key = ((unsigned long long)kh << 32) | kl;
+                fail = fail || (t > 0 && !(key > bound));
+            }
+#pragma unroll
+            for (int uu = 0; uu < KMAX / G; ++uu) {   // (b) no earlier candidate lowers tmp of this one
+                const int u = g + G * uu;
+                const bool near = pdf_f32_ordered(dist_as_written(x, y, z, cent[3 * u + 0], cent[3 * u + 1], cent[3 * u + 2])) < kh;
+                fail = fail || (u < t && near);
+            }
+            unsigned long long fm = __ballot(fail);
+#pragma unroll
+            for (int sft = KMAX; sft < 64; sft <<= 1) fm |= fm >> sft;
+            const unsigned f = (unsigned)fm & ((1u << KMAX) - 1u) & ~1u;       // (candidate 0 is always accepted)
+            const int acc = f ? __ffs(f) - 1 : KMAX;
+            if (lane < acc) idx[sc.start_m + j + lane] = sc.start_n + (int)(~kl & REL_MASK);
             if (lane == 0) cent_n[0] = acc;
+            if (lane < 16) cand[lane] = -1;
         }
         __syncthreads();  // D: the round's centres are published
         const int a = cent_n[0];
@@ -1050,7 +992,6 @@ __global__ __launch_bounds__(64 * NW) void k_fps_mw(const int *__restrict__ offs
         j += a;
         ++n_rounds;
         if (j >= sc.m) break;
-        FPS_TICK(0);
         const unsigned tag = n_rounds;          // > 0, unique per round
         const int q = (int)(n_rounds & 1u);
 
@@ -1098,119 +1039,73 @@ __global__ __launch_bounds__(64 * NW) void k_fps_mw(const int *__restrict__ offs
             }
         }
         __syncthreads();  // A: shared lists complete
-        FPS_TICK(1);
         const int n_bk = (int)cnt[q], n_sup = (int)cnt[2 + q];
         if (tid == 0) { cnt[q ^ 1] = 0u; cnt[2 + (q ^ 1)] = 0u; }   // next round's counters (nobody touches them before barrier C)
         n_supers += n_sup;
         n_updates += n_bk;
 
         // ---- 3. update the claimed buckets with every accepted centre.  This phase is bound by the CU's vector issue (16 waves, one
-        // scene per CU), and most of a bucket's ~150 instructions were the four 64-lane reductions (best and second-best key) with their DPP
-        // wait states.  RANK (round 4): FOUR buckets per pass, one per 16-lane row, four consecutive points per lane -- a lane first
-        // reduces its own four points, the rows then need 4-step reductions, for four buckets at once.
-        if (RANK) {
-            for (int i0 = wave * 4; i0 < n_bk; i0 += NW * 4) {   // (two such sets in flight per wave: measured slower, 22.9 vs 21.7 ms at level 1)
-                const int bk = i0 + row < n_bk ? (int)blist[i0 + row] : -1;
-                const bool live = bk >= 0;
-                const size_t pos = (size_t)sc.pbase + (size_t)(live ? bk : 0) * BSZ + (size_t)col * 4;   // (idle rows read bucket 0, write nothing)
-                float4 p[4];
+        // scene per CU), not by the loads, and with one bucket per wave pass most of a bucket's ~150 instructions were the four 64-lane
+        // reductions (best and second-best key) with their DPP wait states.  So FOUR buckets per pass, one per 16-lane row, four
+        // consecutive points per lane -- a lane first reduces its own four points, the rows then need 4-step reductions, for four buckets
+        // at once.  (More loads in flight never paid in the one-bucket form either -- levels 100k / 25k / 6250: 1 bucket in flight
+        // 23.5 / 7.1 / 2.7 ms, 2: 24.0 / 7.3 / 2.9, 4: 26.6 / 8.6 / 3.1, 8: 30.8 / 11.3 / 4.3.)
+        for (int i0 = wave * 4; i0 < n_bk; i0 += NW * 4) {   // (two such sets in flight per wave: measured slower, 22.9 vs 21.7 ms at level 1)
+            const int bk = i0 + row < n_bk ? (int)blist[i0 + row] : -1;
+            const bool live = bk >= 0;
+            const size_t pos = (size_t)sc.pbase + (size_t)(live ? bk : 0) * BSZ + (size_t)col * 4;   // (idle rows read bucket 0, write nothing)
+            float4 p[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) p[e] = pts[pos + e];
-                const uint4 kb4 = *reinterpret_cast<const uint4 *>(kbs + pos);
-                const unsigned klo[4] = {live ? kb4.x : 0u, live ? kb4.y : 0u, live ? kb4.z : 0u, live ? kb4.w : 0u};
-                unsigned rem = live ? claimB[bk] : 0u;            // centres that reach the row's bucket
-                float w[4] = {p[0].w, p[1].w, p[2].w, p[3].w};
-                while (__ballot(rem != 0u) != 0ull) {             // every row takes ITS next centre (padding points carry w < 0: never lowered)
-                    const bool on = rem != 0u;
-                    const int v = on ? __ffs(rem) - 1 : 0;
-                    rem &= rem - 1u;
-                    const float ux = cent[3 * v + 0], uy = cent[3 * v + 1], uz = cent[3 * v + 2];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float d = dist_as_written(p[e].x, p[e].y, p[e].z, ux, uy, uz);
-                        if (on && d < w[e]) w[e] = d;
-                    }
-                }
-                unsigned long long key[4];
+            for (int e = 0; e < 4; ++e) p[e] = pts[pos + e];
+            const uint4 kb4 = *reinterpret_cast<const uint4 *>(kbs + pos);
+            const unsigned klo[4] = {live ? kb4.x : 0u, live ? kb4.y : 0u, live ? kb4.z : 0u, live ? kb4.w : 0u};
+            unsigned rem = live ? claimB[bk] : 0u;            // centres that reach the row's bucket
+            float w[4] = {p[0].w, p[1].w, p[2].w, p[3].w};
+            while (__ballot(rem != 0u) != 0ull) {             // every row takes ITS next centre (padding points carry w < 0: never lowered)
+                const bool on = rem != 0u;
+                const int v = on ? __ffs(rem) - 1 : 0;
+                rem &= rem - 1u;
+                const float ux = cent[3 * v + 0], uy = cent[3 * v + 1], uz = cent[3 * v + 2];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    if (live && w[e] < p[e].w) reinterpret_cast<float *>(pts + pos + e)[3] = w[e];
-                    key[e] = ((unsigned long long)(live && p[e].w >= 0.f ? pdf_f32_ordered(w[e]) : 0u) << 32) | klo[e];
-                }
-                // the lane's best and second-best point
-                unsigned long long best = key[0], second = 0ull;
-                float bx = p[0].x, by = p[0].y, bz = p[0].z;
-#pragma unroll
-                for (int e = 1; e < 4; ++e) {
-                    const bool gt = key[e] > best;
-                    const unsigned long long lower = gt ? best : key[e];
-                    second = lower > second ? lower : second;
-                    best = gt ? key[e] : best;
-                    bx = gt ? p[e].x : bx; by = gt ? p[e].y : by; bz = gt ? p[e].z : bz;
-                }
-                // the row's best point, and the best of the rest (the winning lane contributes its second-best)
-                const unsigned bh = (unsigned)(best >> 32), bl = (unsigned)best;
-                const unsigned mh = row_umax_bcast(bh, row);
-                const unsigned ml = row_umax_bcast(bh == mh ? bl : 0u, row);
-                const unsigned long long wm = __ballot(bh == mh && bl == ml);
-                const bool iam = col == __ffs((unsigned)(wm >> (16 * row)) & 0xffffu) - 1;
-                const unsigned ch = iam ? (unsigned)(second >> 32) : bh, cl = iam ? (unsigned)second : bl;
-                const unsigned m2h = row_umax_bcast(ch, row);
-                const unsigned m2l = row_umax_bcast(ch == m2h ? cl : 0u, row);
-                if (iam && live) {
-                    claimB[bk] = 0u;
-                    B.khi[bk] = mh; B.klo[bk] = ml;
-                    B.k2hi[bk] = m2h; B.k2lo[bk] = m2l;
-                    B.bx[bk] = bx; B.by[bk] = by; B.bz[bk] = bz;
+                    const float d = dist_as_written(p[e].x, p[e].y, p[e].z, ux, uy, uz);
+                    if (on && d < w[e]) w[e] = d;
                 }
             }
-        } else
-        for (int i0 = wave * UNR; i0 < n_bk; i0 += NW * UNR) {
-            float4 p[UNR];
-            unsigned kb[UNR];
-            int bkid[UNR];
+            unsigned long long key[4];
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                bkid[u] = i0 + u < n_bk ? (int)blist[i0 + u] : -1;
-                if (bkid[u] >= 0) {
-                    const size_t pos = (size_t)sc.pbase + (size_t)bkid[u] * BSZ + lane;
-                    p[u] = pts[pos];
-                    kb[u] = kbs[pos];
-                }
+            for (int e = 0; e < 4; ++e) {
+                if (live && w[e] < p[e].w) reinterpret_cast<float *>(pts + pos + e)[3] = w[e];
+                key[e] = ((unsigned long long)(live && p[e].w >= 0.f ? pdf_f32_ordered(w[e]) : 0u) << 32) | klo[e];
             }
+            // the lane's best and second-best point
+            unsigned long long best = key[0], second = 0ull;
+            float bx = p[0].x, by = p[0].y, bz = p[0].z;
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) {   // (no early exit: the UNR reduction chains are independent and interleave)
-                const bool live = bkid[u] >= 0;
-                const unsigned msk = live ? (unsigned)__builtin_amdgcn_readfirstlane((int)claimB[bkid[u]]) : 0u;   // centres that reach it
-                unsigned khi = 0u;
-                if (live && p[u].w >= 0.f) {
-                    float w = p[u].w;
-#pragma unroll
-                    for (int v = 0; v < KMAX; ++v)
-                        if ((msk >> v) & 1u) {
-                            const float d = dist_as_written(p[u].x, p[u].y, p[u].z, cx[v], cy[v], cz[v]);
-                            if (d < w) w = d;
-                        }
-                    if (w < p[u].w) pts[(size_t)sc.pbase + (size_t)bkid[u] * BSZ + lane].w = w;
-                    khi = pdf_f32_ordered(w);
-                }
-                const unsigned klo = live ? kb[u] : 0u;
-                unsigned mhi, mlo;
-                const int kl = wave_argmax_key(khi, klo, mhi, mlo);
-                const unsigned h2 = lane == kl ? 0u : khi, l2 = lane == kl ? 0u : klo;
-                const unsigned m2hi = wave_umax(h2);
-                const unsigned m2lo = wave_umax(h2 == m2hi ? l2 : 0u);
-                const float nx = lane_bcast(live ? p[u].x : 0.f, kl & 63), ny = lane_bcast(live ? p[u].y : 0.f, kl & 63), nz = lane_bcast(live ? p[u].z : 0.f, kl & 63);
-                if (lane == 0 && live) {
-                    claimB[bkid[u]] = 0u;
-                    B.khi[bkid[u]] = mhi; B.klo[bkid[u]] = mlo;
-                    B.k2hi[bkid[u]] = m2hi; B.k2lo[bkid[u]] = m2lo;
-                    B.bx[bkid[u]] = nx; B.by[bkid[u]] = ny; B.bz[bkid[u]] = nz;
-                }
+            for (int e = 1; e < 4; ++e) {
+                const bool gt = key[e] > best;
+                const unsigned long long lower = gt ? best : key[e];
+                second = lower > second ? lower : second;
+                best = gt ? key[e] : best;
+                bx = gt ? p[e].x : bx; by = gt ? p[e].y : by; bz = gt ? p[e].z : bz;
+            }
+            // the row's best point, and the best of the rest (the winning lane contributes its second-best)
+            const unsigned bh = (unsigned)(best >> 32), bl = (unsigned)best;
+            const unsigned mh = row_umax_bcast(bh, row);
+            const unsigned ml = row_umax_bcast(bh == mh ? bl : 0u, row);
+            const unsigned long long wm = __ballot(bh == mh && bl == ml);
+            const bool iam = col == __ffs((unsigned)(wm >> (16 * row)) & 0xffffu) - 1;
+            const unsigned ch = iam ? (unsigned)(second >> 32) : bh, cl = iam ? (unsigned)second : bl;
+            const unsigned m2h = row_umax_bcast(ch, row);
+            const unsigned m2l = row_umax_bcast(ch == m2h ? cl : 0u, row);
+            if (iam && live) {
+                claimB[bk] = 0u;
+                B.khi[bk] = mh; B.klo[bk] = ml;
+                B.k2hi[bk] = m2h; B.k2lo[bk] = m2l;
+                B.bx[bk] = bx; B.by[bk] = by; B.bz[bk] = bz;
             }
         }
         __syncthreads();  // B: bucket records + tmp stores visible
-        FPS_TICK(2);
 
         // ---- 4. refresh the claimed supers (dealt to the waves, 4 supers per pass)
         for (int g = 4 * wave; g < n_sup; g += 4 * NW) {
@@ -1236,18 +1131,49 @@ __global__ __launch_bounds__(64 * NW) void k_fps_mw(const int *__restrict__ offs
             }
         }
         __syncthreads();  // C: super records complete before the next round's candidates
-        FPS_TICK(3);
     }
-    if (tid == 0 && stats) {
-        stats[blockIdx.x * 4 + 0] = n_updates;
-        stats[blockIdx.x * 4 + 1] = n_supers;
-        stats[blockIdx.x * 4 + 2] = (unsigned)sc.m;
-        stats[blockIdx.x * 4 + 3] = n_rounds;
-#ifdef FPS_PROFILE
-        for (int i = 0; i < 4; ++i) stats[blockIdx.x * 4 + i] = (unsigned)(tc[i] >> 10);   // kilo-cycles: candidates | lists | updates | refresh
-#endif
+    store_stats(stats, n_updates, n_supers, sc.m, n_rounds);
+}
+
+// dynamic LDS of k_fps_mw<waves>, as carved at its top
+size_t lds_mw(int nb_cap, int ns_cap, int waves) {
+    const int nr_cap = nb_cap <= BKC_MAX ? nb_cap : ns_cap;
+    return (size_t)(REC2 * (nb_cap + ns_cap) + nb_cap + ns_cap + 4 + 3 * 16 + 4 + nr_cap + 3 * 16 + 16 * SUP) * 4 +   // records, claimB, claimS, cnt, cent, cent_n, rank, cand + c_s2h + c_s2l, rank2
+           (size_t)(nb_cap + 64 + ns_cap + 64 + waves * list_stride(ns_cap)) * 2;                                    // blist, slist, pslist
+}
+
+// ---------------------------------------------------------------- which kernel, and its launch
+enum Kernel { SINGLE, MULTI, MW8, MW16 };
+
+// The kernel for a launch whose largest scene has n points (nb_cap buckets): the table of the file header.
+// measured (2 scenes, levels 100k / 25k / 6250 / 1562 points): 16 waves 33.0 / 10.0 / 3.9 / 1.7 ms, 8 waves 41.3 / 10.8 / 3.6 / 1.5 ms,
+// the one-sample kernel 91 / 20 / 4.9 / 1.2 ms -> by the size of the largest scene; a kernel whose records do not fit the LDS gives way to
+// the next smaller record (k_fps_mw -> k_fps_multi -> k_fps, which fits up to NB_MAX buckets).
+// PDFOPS_FPS_KERNEL = single | multi | mw8 | mw16 (read at every launch: a test drives every kernel inside one process) takes the place of
+// the choice by size for n >= FPS_MULTI_MIN where the named kernel's records fit; any other value leaves the choice as it is.
+Kernel choose(int n, int nb_cap, int ns_cap) {
+    static const char *const names[] = {"single", "multi", "mw8", "mw16"};   // (indexed by Kernel, like `fits`)
+    const bool fits[] = {true, lds_multi(nb_cap, ns_cap) <= LDS_LIMIT, lds_mw(nb_cap, ns_cap, 8) <= LDS_LIMIT, lds_mw(nb_cap, ns_cap, 16) <= LDS_LIMIT};
+    if (n < FPS_MULTI_MIN) return SINGLE;
+    if (const char *forced = getenv("PDFOPS_FPS_KERNEL"))
+        for (int k = SINGLE; k <= MW16; ++k)
+            if (!strcmp(forced, names[k]) && fits[k]) return (Kernel)k;
+    const Kernel mw = n >= 16384 ? MW16 : MW8;
+    return fits[mw] ? mw : fits[MULTI] ? MULTI : SINGLE;
+}
+
+// One workgroup of `waves` waves per scene.  A launch with more than 64 KB of LDS needs the kernel's limit raised first: once per device
+// (K's own `site`), to the whole LDS, so that it also covers every later launch.  A refused raise is returned as HIP's error.
+template <auto K, typename... Args>
+int launch(int b, int waves, size_t lds, hipStream_t s, Args... args) {
+    static PdfLdsLimit site;
+    const void *fn = reinterpret_cast<const void *>(K);
+    if (lds > 64 * 1024 && !pdf_lds_limit_raised(site, fn, (int)LDS_LIMIT)) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
+        if (e != hipSuccess) return (int)e;
     }
-#undef FPS_TICK
+    K<<<b, 64 * waves, lds, s>>>(args...);
+    return pdf_launch_status();
 }
 
 }  // namespace
@@ -1295,63 +1221,12 @@ extern "C" int pdf_farthest_point_sampling_bucketed(int b, int n, int n_total, c
     // surplus waves summarise unused slots that no scene ever reads
     k_meta<<<L.npad / BSZ, 64, 0, s>>>(pts, kb, meta);
     const int ns_cap = (nb_cap + SUP - 1) / SUP;
-    const size_t lds = (size_t)(11 * nb_cap + 11 * ns_cap) * 4 + (size_t)(2 * (((ns_cap + 63) & ~63) + 64) + nb_cap + 64) * 2;
-    const char *env_nw = getenv("PDFOPS_FPS_NW");  // tuning knob (waves per scene): 1, 2 or 4
-    const int nw = env_nw ? atoi(env_nw) : 4;
     unsigned *stats = reinterpret_cast<unsigned *>(ws + L.stats);
-    // several samples per round (k_fps_multi) when its larger records fit the 160 KB of LDS (scenes up to ~180k points)
-    const size_t lds2 = (size_t)(REC2 * nb_cap + REC2 * ns_cap) * 4 + (size_t)(2 * (((ns_cap + 63) & ~63) + 64) + nb_cap + 64) * 2;
-    const char *env_k = getenv("PDFOPS_FPS_K");    // tuning knob (samples per round): 1 = the one-sample kernel, 4 or 8
-    const int kmulti = env_k ? atoi(env_k) : (n >= FPS_MULTI_MIN ? 8 : 1);
-    // one centre per wave (k_fps_mw<NW>): records + claim tags + shared / private lists
-    const char *env_mw = getenv("PDFOPS_FPS_MW");   // tuning knob: 0 = k_fps_multi, 8 / 16 = waves (= centres per round) of k_fps_mw
-    // measured (2 scenes, levels 100k / 25k / 6250 / 1562 points): 16 waves 33.0 / 10.0 / 3.9 / 1.7 ms, 8 waves 41.3 / 10.8 / 3.6 / 1.5 ms,
-    // the one-sample kernel 91 / 20 / 4.9 / 1.2 ms -> by the size of the largest scene
-    const int mw = env_mw ? atoi(env_mw) : (n >= 16384 ? 16 : n >= FPS_MULTI_MIN ? 8 : 0);
-    const int mww = mw >= 16 ? 16 : 8;
-    const size_t lds3 = (size_t)(REC2 * nb_cap + REC2 * ns_cap + nb_cap + ns_cap + 4 + 3 * 16 + 4 + (nb_cap <= BKC_MAX ? nb_cap : ns_cap) + 3 * 16 + 16 * SUP) * 4 +
-                        (size_t)(nb_cap + 64 + ns_cap + 64 + mww * (((ns_cap + 63) & ~63) + 64)) * 2;
-    if (kmulti > 1 && mw != 0 && lds3 <= 160 * 1024) {
-#define PDF_LAUNCH_FPS_MW(NW_, RANK_)                                                                                     \
-    do {                                                                                                                 \
-        if (lds3 > 64 * 1024) {                                                                                          \
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fps_mw<NW_, RANK_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3); \
-            if (e != hipSuccess) return (int)e;                                                                          \
-        }                                                                                                                \
-        k_fps_mw<NW_, RANK_><<<b, 64 * NW_, lds3, s>>>(offset, new_offset, pts, kb, meta, idx, nb_cap, stats, two_lvl);   \
-    } while (0)
-        static const bool rank_sel = [] { const char *v = getenv("PDFOPS_FPS_RANK"); return !(v && v[0] == '0'); }();   // 0: rounds 2-3 candidate loop (A/B)
-        static const int two_lvl = [] { const char *v = getenv("PDFOPS_FPS_TWO_LEVEL"); return (v && v[0] == '0') ? 0 : 1; }();   // 0: super-bucket candidates at level 1 (A/B)
-        if (rank_sel) { if (mww == 16) PDF_LAUNCH_FPS_MW(16, true); else PDF_LAUNCH_FPS_MW(8, true); }
-        else { if (mww == 16) PDF_LAUNCH_FPS_MW(16, false); else PDF_LAUNCH_FPS_MW(8, false); }
-#undef PDF_LAUNCH_FPS_MW
-        return pdf_launch_status();
+    switch (choose(n, nb_cap, ns_cap)) {
+    case MW16: return launch<k_fps_mw<16>>(b, 16, lds_mw(nb_cap, ns_cap, 16), s, offset, new_offset, pts, kb, meta, idx, nb_cap, stats, 1);
+    case MW8: return launch<k_fps_mw<8>>(b, 8, lds_mw(nb_cap, ns_cap, 8), s, offset, new_offset, pts, kb, meta, idx, nb_cap, stats, 1);
+    case MULTI: return launch<k_fps_multi>(b, FPS_WAVES, lds_multi(nb_cap, ns_cap), s, offset, new_offset, pts, kb, meta, idx, nb_cap, stats);
+    case SINGLE: break;
     }
-    if (kmulti > 1 && lds2 <= 160 * 1024) {
-#define PDF_LAUNCH_FPS_MULTI(NW_, K_)                                                                                    \
-    do {                                                                                                                 \
-        if (lds2 > 64 * 1024) {                                                                                          \
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fps_multi<NW_, K_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-            if (e != hipSuccess) return (int)e;                                                                          \
-        }                                                                                                                \
-        k_fps_multi<NW_, K_><<<b, 64 * NW_, lds2, s>>>(offset, new_offset, pts, kb, meta, idx, nb_cap, stats);            \
-    } while (0)
-        if (kmulti <= 4) { if (nw == 8) PDF_LAUNCH_FPS_MULTI(8, 4); else PDF_LAUNCH_FPS_MULTI(4, 4); }
-        else { if (nw == 8) PDF_LAUNCH_FPS_MULTI(8, 8); else PDF_LAUNCH_FPS_MULTI(4, 8); }
-#undef PDF_LAUNCH_FPS_MULTI
-        return pdf_launch_status();
-    }
-#define PDF_LAUNCH_FPS(NW_)                                                                                              \
-    do {                                                                                                                 \
-        if (lds > 64 * 1024) {                                                                                           \
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fps<NW_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return (int)e;                                                                          \
-        }                                                                                                                \
-        k_fps<NW_><<<b, 64 * NW_, lds, s>>>(offset, new_offset, pts, kb, meta, idx, nb_cap, stats);                       \
-    } while (0)
-    if (nw == 1) PDF_LAUNCH_FPS(1);
-    else if (nw == 2) PDF_LAUNCH_FPS(2);
-    else PDF_LAUNCH_FPS(4);
-#undef PDF_LAUNCH_FPS
-    return pdf_launch_status();
+    return launch<k_fps>(b, FPS_WAVES, lds_single(nb_cap, ns_cap), s, offset, new_offset, pts, kb, meta, idx, nb_cap, stats);
 }

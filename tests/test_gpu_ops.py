@@ -179,8 +179,8 @@ def test_fps_full_size_100k(hip, oracle_backend):
 
 def test_fps_config4_size_and_kernel_variants(hip):
     """ScanNet-shaped 150k -> 37.5k (16-wave multi-sample kernel, LDS-resident records near the 160 KB limit) and a 3-scene batch whose
-    scenes fall into the three kernel classes (>= 16k points: 16 waves, >= 3k: 8 waves, below: the one-sample kernel -- chosen by
-    the LARGEST scene) against the plain reference-shaped kernel; every PDFOPS_FPS_MW / PDFOPS_FPS_K variant gives the same indices."""
+    scenes fall into the three kernel classes (>= 16,384 points: 16 waves, >= 768: 8 waves, below: the one-sample kernel -- chosen by
+    the LARGEST scene) against the plain reference-shaped kernel; every kernel PDFOPS_FPS_KERNEL can force gives the same indices."""
     from pointcloudpdf_amd import synthetic
 
     xyz = torch.from_numpy(synthetic.make_scene(150000, 11, kind="scannet")["coord"]).to(DEV)
@@ -196,7 +196,13 @@ def test_fps_config4_size_and_kernel_variants(hip):
         hip.fps_mode = "plain"
         want3 = hip.farthest_point_sampling(pts, o3, n3, max(sizes), sum(msizes))
         hip.fps_mode = "bucketed"
-        for env in ({}, {"PDFOPS_FPS_MW": "8"}, {"PDFOPS_FPS_MW": "16"}, {"PDFOPS_FPS_MW": "0"}, {"PDFOPS_FPS_K": "1"}, {"PDFOPS_FPS_MW": "0", "PDFOPS_FPS_K": "4"}):
+        # The work counters tell that the named kernel really ran (an unknown or ignored name would fall back to the automatic choice):
+        # their fourth word is the scene's bucket count for k_fps and the round count for the others -- a round accepts 1 .. K samples
+        # after the first, so (m - 1) / K <= rounds <= m - 1, and three kernels that differ in K or in their candidate units do not
+        # need the same number of rounds for the 5,000 samples of the first scene.
+        rounds = {}
+        hip.collect_fps_stats = True
+        for env in ({}, {"PDFOPS_FPS_KERNEL": "mw8"}, {"PDFOPS_FPS_KERNEL": "mw16"}, {"PDFOPS_FPS_KERNEL": "multi"}, {"PDFOPS_FPS_KERNEL": "single"}):
             os.environ.update(env)
             try:
                 got = hip.farthest_point_sampling(pts, o3, n3, max(sizes), sum(msizes))
@@ -204,8 +210,17 @@ def test_fps_config4_size_and_kernel_variants(hip):
                 for k_ in env:
                     os.environ.pop(k_, None)
             assert torch.equal(got, want3), env
-        # 170k points: the one-centre-per-wave records no longer fit the LDS -> k_fps_multi; 200k: bucket records do not fit -> plain kernel
-        for n in (170000, 200000):
+            st = hip.last_fps_stats.tolist()
+            assert [row[2] for row in st] == msizes, (env, st)
+            rounds[env.get("PDFOPS_FPS_KERNEL", "auto")] = st[0][3]
+        assert rounds["single"] == (sizes[0] + 63) // 64, rounds
+        for name, k in (("multi", 8), ("mw8", 8), ("mw16", 16)):
+            assert -(-(msizes[0] - 1) // k) <= rounds[name] <= msizes[0] - 1 and rounds[name] != rounds["single"], rounds
+        assert len({rounds["multi"], rounds["mw8"], rounds["mw16"]}) == 3, rounds
+        hip.collect_fps_stats = False
+        # 170k points: the one-centre-per-wave records no longer fit the LDS -> k_fps_multi; 190k: nor do the 13-word records -> k_fps
+        # (with a raised LDS limit); 200k: bucket records do not fit -> plain kernel
+        for n in (170000, 190000, 200000):
             big = torch.from_numpy(synthetic.make_scene(n, 12, kind="scannet")["coord"]).to(DEV)
             ob, nb = offs([n]).to(DEV), offs([n // 4]).to(DEV)
             hip.fps_mode = "plain"
@@ -214,6 +229,7 @@ def test_fps_config4_size_and_kernel_variants(hip):
             assert torch.equal(hip.farthest_point_sampling(big, ob, nb, n, n // 4), wb), n
     finally:
         hip.fps_mode = "bucketed"
+        hip.collect_fps_stats = False
 
 
 # ----------------------------------------------------------------------------------------------- ball queries
