@@ -48,8 +48,9 @@ extern "C" {
  * 11 = pdf_openset_metrics_workspace_bytes / pdf_openset_metrics added (no existing parameter list changed);
  * 12 = pdf_scene_bounds / pdf_window_keys_scene added (no existing parameter list changed);
  * 13 = pdf_criteria_workspace_floats / pdf_ce_ex_* / pdf_focal_* / pdf_dice_* / pdf_bfocal_* added (no existing parameter list changed);
- * 14 = pdf_grid_pool_* / pdf_grid_unpool_forward / pdf_gva_* added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 14
+ * 14 = pdf_grid_pool_* / pdf_grid_unpool_forward / pdf_gva_* added (no existing parameter list changed);
+ * 15 = pdf_cac_* added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 15
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -422,6 +423,45 @@ int pdf_dice_backward(long n, int c, const float *prob, const long *target, long
 int pdf_bfocal_forward(long n, const float *pred, const float *target, float alpha, float gamma, int logits, int reduce, float *grad,
                        float *acc, float *loss, void *stream);
 int pdf_bfocal_backward(long n, const float *dpred, const float *acc, const float *gy, int reduce, float *grad_out, void *stream);
+
+/* Head of the context-aware classifier (pointcept/models/context_aware_classifier/context_aware_classifier_v1m1_base.py) as capturable
+ * passes (csrc/cac.hip): n rows in `scenes` scenes (offset: the scenes' ends, int32 on the device), K classes, c channels, fp32 data,
+ * int64 labels.  No float atomics (chunk slabs added in a fixed order: bit-reproducible), nothing to zero, no host read.  The fused
+ * class is pdf_cac_supported(K, c): c a multiple of 4 up to 64, K <= 256, the (K, c) slab and its row tiles within LDS -- it contains
+ * (20, 48), (13, 48), (13, 24) and (200, 48).  ws: pdf_cac_workspace_floats(n, K, c, scenes) floats.  n < 1, scenes < 1, a NULL array
+ * or a shape outside the class: PDF_ERR_BAD_ARG before any launch.
+ *   soft prototypes: w_nk = softmax(logits_n)_k [max_k softmax >= conf_thresh] (conf_thresh <= 0: no mask), mass[s, k] = sum_{n in s} w_nk,
+ *     proto[s, k, :] = sum_{n in s} w_nk feat_n / (mass + 1e-7).  Backward: gfeat (n, c) and, unless glogits is NULL, the gradient through
+ *     the softmax and the normaliser into the logits (the mask is not differentiated).
+ *   label prototypes: proto[k] = sum_{t_n = k} feat_n / (count_k + 1e-4) where count_k > 0, else base[k]; labels outside [0, K) are skipped.
+ *     Backward: gfeat_n = gproto[t_n] / (count + 1e-4).
+ *   cosine logits: out[n, k] = scale * normalize(x_n) . normalize(proto[s(n), k]) (F.normalize: max(norm, 1e-12)); scenes == 1: one
+ *     prototype set, offset may be NULL.  Backward: gx and gproto, F.normalize's backward with its clamp branch.
+ *   distillation loss (K <= 256, any c): l_n = -sum_k log_softmax(pred)_nk (smoothness softmax(soft)_nk + (1 - smoothness) onehot_nk),
+ *     e_n = -sum_k sm_nk log(sm_nk + 1e-4); loss[0] = sum over the classes present among labels != -1 of
+ *     (sum_{t=y} l e / (sum_{t=y} e + 1e-4)) / (#present + 1e-4), 0 when none is.  grad (n*K) receives the unscaled gradient, rowbuf (2 n)
+ *     the row pairs, acc (pdf_cac_distill_workspace_floats(K) floats, 8-byte aligned) the class triples and coefficients.  A label that
+ *     is neither -1 nor in [0, K) makes the loss NaN.  Backward: grad_out = grad * coefficient[t_n] * gy[0] (only reads). */
+int pdf_cac_supported(int K, int c);
+long pdf_cac_workspace_floats(long n, int K, int c, int scenes);
+int pdf_cac_soft_proto_forward(long n, int K, int c, int scenes, const float *feat, const float *logits, const int *offset,
+                               float conf_thresh, float *proto, float *mass, float *ws, void *stream);
+int pdf_cac_soft_proto_backward(long n, int K, int c, int scenes, const float *feat, const float *logits, const int *offset,
+                                float conf_thresh, const float *proto, const float *mass, const float *gproto, float *gfeat,
+                                float *glogits, void *stream);
+int pdf_cac_label_proto_forward(long n, int K, int c, const float *feat, const long *target, const float *base, float *proto,
+                                float *count, float *ws, void *stream);
+int pdf_cac_label_proto_backward(long n, int K, int c, const long *target, const float *count, const float *gproto, float *gfeat,
+                                 void *stream);
+int pdf_cac_cosine_forward(long n, int K, int c, int scenes, const float *x, const float *proto, const int *offset, float scale,
+                           float *out, void *stream);
+int pdf_cac_cosine_backward(long n, int K, int c, int scenes, const float *x, const float *proto, const int *offset, float scale,
+                            const float *gout, float *gx, float *gproto, float *ws, void *stream);
+long pdf_cac_distill_workspace_floats(int K);
+int pdf_cac_distill_forward(long n, int K, const float *pred, const float *soft, const long *target, float smoothness, float *grad,
+                            float *rowbuf, float *acc, float *loss, void *stream);
+int pdf_cac_distill_backward(long n, int K, const float *grad, const long *target, const float *acc, const float *gy, float *grad_out,
+                             void *stream);
 
 /* Distillation loss of the incremental learner (pointcept/incrLearners/ours/pointpdf_incr_v1m1_base.py:62-87, IncrDistillKlLoss):
  * student (n, cs) and teacher (n, ct) fp32 logits, labels (n) int64, ct <= cs <= 64.  Target row t = [softmax(teacher * inv_tt), 0 ..]

@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 14   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 15   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -141,6 +141,15 @@ _HIP_ONLY_PROTOS = {
     "gva_relation_backward": "llii" + "p" * 10,
     "gva_attend_forward": "lliii" + "p" * 6,
     "gva_attend_backward": "lliii" + "p" * 10,
+    # csrc/cac.hip
+    "cac_soft_proto_forward": "liiipppfppp",
+    "cac_soft_proto_backward": "liiipppfppppp",
+    "cac_label_proto_forward": "liipppppp",
+    "cac_label_proto_backward": "liipppp",
+    "cac_cosine_forward": "liiipppfp",
+    "cac_cosine_backward": "liiipppfpppp",
+    "cac_distill_forward": "lipppfpppp",
+    "cac_distill_backward": "lippppp",
 }
 _KIND = {"i": c_int, "l": c_long, "f": c_float, "d": c_double, "p": c_void_p}
 
@@ -696,6 +705,12 @@ class HipBackend(CBackend):
         lib.pdf_ce_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pdf_criteria_workspace_floats.restype = c_long
         lib.pdf_criteria_workspace_floats.argtypes = [c_int]
+        lib.pdf_cac_supported.restype = c_int
+        lib.pdf_cac_supported.argtypes = [c_int, c_int]
+        lib.pdf_cac_workspace_floats.restype = c_long
+        lib.pdf_cac_workspace_floats.argtypes = [c_long, c_int, c_int, c_int]
+        lib.pdf_cac_distill_workspace_floats.restype = c_long
+        lib.pdf_cac_distill_workspace_floats.argtypes = [c_int]
         lib.pdf_incr_kl_workspace_floats.restype = c_long
         lib.pdf_incr_kl_workspace_floats.argtypes = []
         lib.pdf_incr_kl_forward.restype = c_int
@@ -1964,6 +1979,117 @@ class HipBackend(CBackend):
         require_current_device(dpred, acc, gy)
         out = self._new(dpred, (n,), torch.float32)
         self._call("bfocal_backward", n, dpred, acc, gy, int(bool(reduce)), out)
+        return out
+
+    # -- context-aware classifier head (csrc/cac.hip; pointcloudpdf_amd/cac.py drives them) ----------------------------------------------
+    def cac_supported(self, K, c):
+        return bool(self.lib.pdf_cac_supported(int(K), int(c)))
+
+    def _cac_ws(self, like, n, K, c, scenes):
+        # every float is written before it is read (csrc/cac.hip): nothing to zero, no memset node in a captured step
+        return self._new(like, (int(self.lib.pdf_cac_workspace_floats(int(n), int(K), int(c), int(scenes))),), torch.float32)
+
+    def _cac_shapes(self, rows, cols, K, what):
+        _check(rows, torch.float32, what)
+        n, c = rows.shape
+        if n < 1 or cols.shape[0] != n or not self.cac_supported(K, c):
+            raise ValueError(f"{what}: ({n}, {c}) rows against {tuple(cols.shape)} with {K} classes is outside the fused class")
+        return n, c
+
+    def cac_soft_proto_forward(self, feat, logits, offset, conf_thresh):
+        """-> proto (scenes, K, c), mass (scenes, K)."""
+        _check(logits, torch.float32, "logits"); _check(offset, torch.int32, "offset")
+        K, scenes = logits.shape[1], offset.shape[0]
+        n, c = self._cac_shapes(feat, logits, K, "cac_soft_proto_forward")
+        require_current_device(feat, logits, offset)
+        proto = self._new(feat, (scenes, K, c), torch.float32)
+        mass = self._new(feat, (scenes, K), torch.float32)
+        ws = self._cac_ws(feat, n, K, c, scenes)
+        self._call("cac_soft_proto_forward", n, K, c, scenes, feat, logits, offset, float(conf_thresh), proto, mass, ws)
+        return proto, mass
+
+    def cac_soft_proto_backward(self, feat, logits, offset, conf_thresh, proto, mass, gproto, want_logits):
+        _check(gproto, torch.float32, "grad_output")
+        K, scenes = logits.shape[1], offset.shape[0]
+        n, c = self._cac_shapes(feat, logits, K, "cac_soft_proto_backward")
+        require_current_device(feat, logits, offset, gproto)
+        gfeat = self._new(feat, (n, c), torch.float32)
+        glogits = self._new(feat, (n, K), torch.float32) if want_logits else None
+        self._call("cac_soft_proto_backward", n, K, c, scenes, feat, logits, offset, float(conf_thresh), proto, mass, gproto, gfeat,
+                   ctypes.c_void_p(None) if glogits is None else glogits)
+        return gfeat, glogits
+
+    def cac_label_proto_forward(self, feat, target, base):
+        """-> proto (K, c), count (K)."""
+        _check(target, torch.int64, "target"); _check(base, torch.float32, "base")
+        K = base.shape[0]
+        n, c = self._cac_shapes(feat, target, K, "cac_label_proto_forward")
+        if base.shape != (K, c):
+            raise ValueError(f"cac_label_proto_forward: base {tuple(base.shape)} for {c} channels")
+        require_current_device(feat, target, base)
+        proto = self._new(feat, (K, c), torch.float32)
+        count = self._new(feat, (K,), torch.float32)
+        self._call("cac_label_proto_forward", n, K, c, feat, target, base, proto, count, self._cac_ws(feat, n, K, c, 1))
+        return proto, count
+
+    def cac_label_proto_backward(self, target, count, gproto):
+        _check(gproto, torch.float32, "grad_output")
+        n, (K, c) = target.shape[0], gproto.shape
+        require_current_device(target, count, gproto)
+        gfeat = self._new(gproto, (n, c), torch.float32)
+        self._call("cac_label_proto_backward", n, K, c, target, count, gproto, gfeat)
+        return gfeat
+
+    @staticmethod
+    def _cac_proto(proto, offset):
+        _check(proto, torch.float32, "proto")
+        if offset is not None:
+            _check(offset, torch.int32, "offset")
+        scenes = 1 if proto.dim() == 2 else proto.shape[0]
+        if proto.dim() == 3 and (offset is None or offset.shape[0] != scenes):
+            raise ValueError("cosine logits: per-scene prototypes (scenes, K, c) need the scenes' offset")
+        return scenes, proto.shape[-2], ctypes.c_void_p(None) if proto.dim() == 2 else offset
+
+    def cac_cosine_forward(self, x, proto, offset, scale):
+        scenes, K, off = self._cac_proto(proto, offset)
+        n, c = self._cac_shapes(x, x, K, "cac_cosine_forward")
+        if proto.shape[-1] != c:
+            raise ValueError(f"cac_cosine_forward: prototypes of {proto.shape[-1]} channels for rows of {c}")
+        require_current_device(x, proto, offset)
+        out = self._new(x, (n, K), torch.float32)
+        self._call("cac_cosine_forward", n, K, c, scenes, x, proto, off, float(scale), out)
+        return out
+
+    def cac_cosine_backward(self, x, proto, offset, scale, gout):
+        _check(gout, torch.float32, "grad_output")
+        scenes, K, off = self._cac_proto(proto, offset)
+        n, c = self._cac_shapes(x, gout, K, "cac_cosine_backward")
+        require_current_device(x, proto, offset, gout)
+        gx = self._new(x, (n, c), torch.float32)
+        gproto = self._new(x, tuple(proto.shape), torch.float32)
+        self._call("cac_cosine_backward", n, K, c, scenes, x, proto, off, float(scale), gout, gx, gproto, self._cac_ws(x, n, K, c, scenes))
+        return gx, gproto
+
+    def cac_distill_forward(self, pred, soft, target, smoothness):
+        """-> loss (scalar), grad (n, K) unscaled, acc."""
+        n, K = self._logits_labels(pred, target, "cac_distill_forward")
+        _check(soft, torch.float32, "soft")
+        if soft.shape != pred.shape or K > 256:
+            raise ValueError(f"cac_distill_forward: pred {tuple(pred.shape)}, soft {tuple(soft.shape)} (at most 256 classes)")
+        require_current_device(pred, soft, target)
+        grad = self._new(pred, (n, K), torch.float32)
+        rowbuf = self._new(pred, (n, 2), torch.float32)
+        acc = self._new(pred, (int(self.lib.pdf_cac_distill_workspace_floats(int(K))),), torch.float32)
+        loss = self._new(pred, (), torch.float32)
+        self._call("cac_distill_forward", n, K, pred, soft, target, float(smoothness), grad, rowbuf, acc, loss)
+        return loss, grad, acc
+
+    def cac_distill_backward(self, grad, target, acc, gy):
+        _check(gy, torch.float32, "grad_output")
+        n, K = grad.shape
+        require_current_device(grad, target, acc, gy)
+        out = self._new(grad, (n, K), torch.float32)
+        self._call("cac_distill_backward", n, K, grad, target, acc, gy, out)
         return out
 
     # -- batched test-time fragments (csrc/fragments.hip; pointcloudpdf_amd/testing.py drives them) ------------------------------------

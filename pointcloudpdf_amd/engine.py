@@ -103,6 +103,10 @@ class OpenSegStep(nn.Module):
         if model_cfg is None or rec_cfg is None:
             raise KeyError("build_open_seg_step: the config needs a `model` and a `recognizer` section")
         model_cfg, rec_cfg = dict(model_cfg), dict(rec_cfg)
+        if model_cfg.get("type") == "CAC-v1m1":
+            raise NotImplementedError("build_open_seg_step: open-set scoring over a CAC-v1m1 model is not provided -- its `backbone` hook "
+                                      "hands features, not logits, to the recognizer, and no reference recipe combines the two; use "
+                                      "build_seg_step for the semseg-cac-* configs")
         # (the ScanNet / S3DIS PT-v1 recipes hand PointPdf-v1m1 a `use_existing_nn` that upstream's class does not take either)
         if rec_cfg.get("type") == "PointPdf-v1m1" and rec_cfg.pop("use_existing_nn", None) is not None:
             log.info("build_open_seg_step: recognizer argument `use_existing_nn` is not an argument of PointPdf-v1m1: dropped")
@@ -151,6 +155,33 @@ class OpenSegStep(nn.Module):
 def build_open_seg_step(cfg):
     """``OpenSegStep.from_config(cfg)``: the training step of a reference open-world config, next to ``build_optimizer`` / ``build_scheduler``."""
     return OpenSegStep.from_config(cfg)
+
+
+class SegStep(nn.Module):
+    """The step of a plain ``semseg-*`` config: one model (``DefaultSegmentor`` or ``CAC-v1m1``), no recognizer.  Train mode returns
+    ``dict(loss, <the model's named loss terms, detached>)``, any other mode the model's own dict; ``build_optimizer`` and
+    ``TrainStep(step, optimizer, graph=False)`` take it."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+
+    def forward(self, batch):
+        with dense.deferred_counters():   # BatchNorm step counters: one multi-tensor add per step
+            out = self.model(dict(batch))
+        if not self.training:
+            return out
+        return dict(loss=out["loss"], **{k: v.detach() for k, v in out.items() if k != "loss"})
+
+
+def build_seg_step(cfg):
+    """``SegStep`` of a reference config that has only a ``model`` section (configs/*/semseg-*.py; dict or attribute access)."""
+    from . import cac, point_transformer_v2, stratified  # noqa: F401  (register CAC-v1m1, PT-v2m2, ST-v1m1)
+
+    model_cfg = _cfg_get(cfg, "model")
+    if model_cfg is None:
+        raise KeyError("build_seg_step: the config needs a `model` section")
+    return SegStep(MODELS.build(dict(model_cfg)))
 
 
 class IncrSegStep(nn.Module):
