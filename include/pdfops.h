@@ -49,8 +49,9 @@ extern "C" {
  * 12 = pdf_scene_bounds / pdf_window_keys_scene added (no existing parameter list changed);
  * 13 = pdf_criteria_workspace_floats / pdf_ce_ex_* / pdf_focal_* / pdf_dice_* / pdf_bfocal_* added (no existing parameter list changed);
  * 14 = pdf_grid_pool_* / pdf_grid_unpool_forward / pdf_gva_* added (no existing parameter list changed);
- * 15 = pdf_cac_* added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 15
+ * 15 = pdf_cac_* added (no existing parameter list changed);
+ * 16 = pdf_spconv_* added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 16
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -462,6 +463,53 @@ int pdf_cac_distill_forward(long n, int K, const float *pred, const float *soft,
                             float *rowbuf, float *acc, float *loss, void *stream);
 int pdf_cac_distill_backward(long n, int K, const float *grad, const long *target, const float *acc, const float *gy, float *grad_out,
                              void *stream);
+
+/* Sparse 3-D convolutions (csrc/sparse_conv.hip; DESIGN.md "Sparse convolutions"): the three spconv operators of SpUNet-v1m1 over sites
+ * indices (n, 4) int32 = [batch, d0, d1, d2], fp32 features, weights (C_out, k, k, k, C_in) with the offset's flat index (o0 k + o1) k + o2.
+ * Keys: batch << 48 | d0 << 32 | d1 << 16 | d2 -- coordinates in [0, 65536), batch in [0, 32768).  No float atomics, fixed summation
+ * orders, nothing allocated, every launch on `stream`.
+ * Geometry (coordinate-only).  Every array is sized by the fine level (nmax rows); a level's count is an int on the device that the
+ * kernels read there, so all levels are enqueued without a host read and the caller reads the counts and the status word once.
+ *   pdf_spconv_sort_sites: skey (n) uint64 ascending keys, order (n) int32 the rows in that order (stable: equal sites keep their row
+ *     order); status |= 1 a negative coordinate / batch, 2 a value outside the packing, 4 a duplicated site (never cleared here).
+ *   pdf_spconv_subm_table: nbr (count, ksize^3) int32, entry [i, o] = the row of the site at coord_i + o - ksize / 2 of the same batch (the
+ *     lowest row of a duplicated site), -1 where none is.  order NULL: the rows are in key order themselves (every coarse level).
+ *   pdf_spconv_down: one kernel-2 stride-2 step.  limit (3 host ints or NULL): coarse sites outside it are dropped, their fine rows get
+ *     parent -1.  -> parent / code (nmax), the coarse sites in ascending key order (coarse_indices (nmax, 4), coarse_skey), children
+ *     (nmax, 8; -1: none; the lowest row of a duplicated site), the fine rows bucketed by code in tiles of 128 rows (bucket_perm:
+ *     pdf_spconv_bucket_rows(nmax) ints, -1 padding; tile_code: one int per tile, -1 past the last bucket; bucket_ptr: 18 ints),
+ *     count_out[0] = the number of coarse sites.  workspace: pdf_spconv_geometry_workspace_bytes(nmax) bytes, 256-byte aligned.
+ * Products.  pdf_spconv_supported(k, cin, cout): 1 = the matrix-core class (cin, cout multiples of 32 up to 384, k <= 3), 2 = the small
+ *   class of the stem (cin <= 16, cout 32 or 64, k <= 5), 0 = neither.
+ *   pdf_spconv_gather: out[row, :] = bias + sum_k x[tbl[row, mirror ? K - 1 - k : k], :] . W_k over rows `row = perm ? perm[r] : r`,
+ *     r < rows, 0 <= row < orows; table entries outside [0, xrows) read zeros; W_k element (kk, col) = w[kk w_kk + k w_k + col w_col];
+ *     K <= 27.  tile_k (needs perm, K == 1): tile t of 128 list entries uses the tap tile_k[t] (a tile with tile_k < 0 is skipped) --
+ *     the selected-weight product out[i] = x[parent[i]] W[code[i]] over pdf_spconv_down's buckets.
+ *   pdf_spconv_small_forward / _dgrad: the same sum and its input gradient (through the mirrored table) for the small class.
+ *   pdf_spconv_wgrad: dw (C_out, K, C_in) = sum_r G[tbl[r, k], :]^T D[r, :]; swap = 0: G = the input (ca = C_in), D = the output gradient
+ *     (cb = C_out); swap = 1: G = the output gradient, D = the input.  cb a multiple of 32 up to 384, ca <= 384.  ws:
+ *     pdf_spconv_wgrad_ws_floats floats of partial slabs, added in slab order.
+ *   pdf_spconv_colsum: out[c] = sum_r g[r, c] (the bias gradient): chunk sums, then the chunks in order; ws: pdf_spconv_colsum_ws_floats. */
+long pdf_spconv_geometry_workspace_bytes(long n);
+long pdf_spconv_bucket_rows(long n);
+int pdf_spconv_sort_sites(long n, const int *indices, unsigned long long *skey, int *order, int *status, void *workspace, void *stream);
+int pdf_spconv_subm_table(long nmax, const int *count, const int *indices, const unsigned long long *skey, const int *order, int ksize,
+                          int *nbr, void *stream);
+int pdf_spconv_down(long nmax, const int *count, const int *indices, const int *limit, int *parent, int *code, int *coarse_indices,
+                    unsigned long long *coarse_skey, int *children, int *bucket_perm, int *tile_code, int *bucket_ptr, int *count_out,
+                    void *workspace, void *stream);
+int pdf_spconv_supported(int k, int cin, int cout);
+int pdf_spconv_gather(long rows, long orows, long xrows, int cin, int cout, int K, const float *x, const int *tbl, int mirror,
+                      const int *perm, const int *tile_k, const float *w, long w_kk, long w_k, long w_col, const float *bias, float *out,
+                      void *stream);
+int pdf_spconv_small_forward(long rows, int cin, int cout, int K, const float *x, const int *tbl, const float *w, const float *bias,
+                             float *out, void *stream);
+int pdf_spconv_small_dgrad(long rows, int cin, int cout, int K, const float *g, const int *tbl, const float *w, float *dx, void *stream);
+long pdf_spconv_wgrad_ws_floats(long rows, int K, int ca, int cb);
+int pdf_spconv_wgrad(long rows, long grows, int K, int ca, int cb, const float *G, const float *D, const int *tbl, int swap, float *ws,
+                     float *dw, void *stream);
+long pdf_spconv_colsum_ws_floats(int c);
+int pdf_spconv_colsum(long rows, int c, const float *g, float *ws, float *out, void *stream);
 
 /* Distillation loss of the incremental learner (pointcept/incrLearners/ours/pointpdf_incr_v1m1_base.py:62-87, IncrDistillKlLoss):
  * student (n, cs) and teacher (n, ct) fp32 logits, labels (n) int64, ct <= cs <= 64.  Target row t = [softmax(teacher * inv_tt), 0 ..]

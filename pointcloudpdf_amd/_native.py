@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 15   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 16   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -150,6 +150,15 @@ _HIP_ONLY_PROTOS = {
     "cac_cosine_backward": "liiipppfpppp",
     "cac_distill_forward": "lipppfpppp",
     "cac_distill_backward": "lippppp",
+    # csrc/sparse_conv.hip
+    "spconv_sort_sites": "lppppp",
+    "spconv_subm_table": "lppppip",
+    "spconv_down": "l" + "p" * 13,
+    "spconv_gather": "llliiippippplllpp",
+    "spconv_small_forward": "liiippppp",
+    "spconv_small_dgrad": "liiipppp",
+    "spconv_wgrad": "lliiipppipp",
+    "spconv_colsum": "lippp",
 }
 _KIND = {"i": c_int, "l": c_long, "f": c_float, "d": c_double, "p": c_void_p}
 
@@ -711,6 +720,16 @@ class HipBackend(CBackend):
         lib.pdf_cac_workspace_floats.argtypes = [c_long, c_int, c_int, c_int]
         lib.pdf_cac_distill_workspace_floats.restype = c_long
         lib.pdf_cac_distill_workspace_floats.argtypes = [c_int]
+        lib.pdf_spconv_supported.restype = c_int
+        lib.pdf_spconv_supported.argtypes = [c_int, c_int, c_int]
+        lib.pdf_spconv_geometry_workspace_bytes.restype = c_long
+        lib.pdf_spconv_geometry_workspace_bytes.argtypes = [c_long]
+        lib.pdf_spconv_bucket_rows.restype = c_long
+        lib.pdf_spconv_bucket_rows.argtypes = [c_long]
+        lib.pdf_spconv_wgrad_ws_floats.restype = c_long
+        lib.pdf_spconv_wgrad_ws_floats.argtypes = [c_long, c_int, c_int, c_int]
+        lib.pdf_spconv_colsum_ws_floats.restype = c_long
+        lib.pdf_spconv_colsum_ws_floats.argtypes = [c_int]
         lib.pdf_incr_kl_workspace_floats.restype = c_long
         lib.pdf_incr_kl_workspace_floats.argtypes = []
         lib.pdf_incr_kl_forward.restype = c_int
@@ -2090,6 +2109,101 @@ class HipBackend(CBackend):
         require_current_device(grad, target, acc, gy)
         out = self._new(grad, (n, K), torch.float32)
         self._call("cac_distill_backward", n, K, grad, target, acc, gy, out)
+        return out
+
+    # -- sparse convolutions (csrc/sparse_conv.hip; pointcloudpdf_amd/sparse_conv.py drives them) ------------------------------------------
+    def spconv_supported(self, k, cin, cout):
+        """0: no HIP pass, 1: the matrix-core class, 2: the small-C_in class (the stem)."""
+        return int(self.lib.pdf_spconv_supported(int(k), int(cin), int(cout)))
+
+    def spconv_geometry(self, indices, levels, subm_sizes, limits=None):
+        """All levels of a stride-2 pyramid over ``indices`` (n, 4) int32 in ONE submission and ONE host read (the counts and the status
+        word).  subm_sizes[l]: the kernel sizes whose neighbour tables level l gets; limits[l]: the coarse spatial shape of step l -> l + 1
+        or None.  -> (status, [level dict], [step dict]); arrays are views of buffers sized by the fine level."""
+        _check(indices, torch.int32, "indices")
+        require_current_device(indices)
+        n = indices.shape[0]
+        dev = indices.device
+        new = lambda shape, dtype=torch.int32: torch.empty(shape, dtype=dtype, device=dev)
+        counts = torch.tensor([0, n] + [0] * (levels - 1), dtype=torch.int32, device=dev)   # [status | count of every level]
+        ws = new((int(self.lib.pdf_spconv_geometry_workspace_bytes(n)),), torch.uint8)
+        padded = int(self.lib.pdf_spconv_bucket_rows(n))
+        lv = [dict(indices=indices, skey=new((n,), torch.int64), order=new((n,)), nbr={})]
+        self._call("spconv_sort_sites", n, indices, lv[0]["skey"], lv[0]["order"], counts, ws)
+        steps = []
+        for l in range(levels):
+            cur = lv[l]
+            for ks in subm_sizes[l]:
+                cur["nbr"][ks] = new((n, ks ** 3))
+                self._call("spconv_subm_table", n, counts[1 + l:], cur["indices"], cur["skey"],
+                           cur["order"] if cur["order"] is not None else ctypes.c_void_p(None), int(ks), cur["nbr"][ks])
+            if l == levels - 1:
+                break
+            st = dict(parent=new((n,)), code=new((n,)), children=new((n, 8)), bucket_perm=new((padded,)), tile_code=new((padded // 128,)),
+                      bucket_ptr=new((18,)))
+            nxt = dict(indices=new((n, 4)), skey=new((n,), torch.int64), order=None, nbr={})
+            lim = None if not limits or limits[l] is None else (ctypes.c_int * 3)(*[int(v) for v in limits[l]])
+            self._call("spconv_down", n, counts[1 + l:], cur["indices"], lim, st["parent"], st["code"], nxt["indices"], nxt["skey"],
+                       st["children"], st["bucket_perm"], st["tile_code"], st["bucket_ptr"], counts[2 + l:], ws)
+            st["truncated"] = lim is not None
+            steps.append(st)
+            lv.append(nxt)
+        host = counts.tolist()   # the one host read of a geometry build
+        status, cnt = host[0], host[1:]
+        for l, cur in enumerate(lv):
+            cur["n"] = cnt[l]
+            cur["indices"] = cur["indices"][:cnt[l]]
+            cur["nbr"] = {ks: t[:cnt[l]] for ks, t in cur["nbr"].items()}
+        for l, st in enumerate(steps):
+            st["parent"], st["code"], st["children"] = st["parent"][:cnt[l]], st["code"][:cnt[l]], st["children"][:cnt[l + 1]]
+            st["bucket_rows"] = int(self.lib.pdf_spconv_bucket_rows(cnt[l]))
+        return status, lv, steps
+
+    def spconv_gather(self, x, tbl, weight, bias, orows, transposed, mirror=False, perm=None, tile_k=None, rows=None, zero=False):
+        """pdf_spconv_gather over weight (C_out, K, C_in): transposed = False: x (., C_in) -> (orows, C_out); True: x (., C_out) -> (orows, C_in)."""
+        co, K, ci = weight.shape
+        cin, cout = (co, ci) if transposed else (ci, co)
+        strides = (K * ci, ci, 1) if transposed else (1, ci, K * ci)
+        require_current_device(x, tbl, weight)
+        out = self._new(x, (orows, cout), torch.float32, zero=zero)
+        Kt = 1 if tbl.dim() == 1 else tbl.shape[1]
+        null = ctypes.c_void_p(None)
+        self._call("spconv_gather", int(orows if rows is None else rows), int(orows), x.shape[0], cin, cout, Kt, x, tbl, int(bool(mirror)),
+                   null if perm is None else perm, null if tile_k is None else tile_k, weight, *strides, null if bias is None else bias, out)
+        return out
+
+    def spconv_small_forward(self, x, tbl, weight, bias):
+        co, K, ci = weight.shape
+        require_current_device(x, tbl, weight)
+        out = self._new(x, (x.shape[0], co), torch.float32)
+        self._call("spconv_small_forward", x.shape[0], ci, co, K, x, tbl, weight, ctypes.c_void_p(None) if bias is None else bias, out)
+        return out
+
+    def spconv_small_dgrad(self, g, tbl, weight):
+        co, K, ci = weight.shape
+        require_current_device(g, tbl, weight)
+        out = self._new(g, (g.shape[0], ci), torch.float32)
+        self._call("spconv_small_dgrad", g.shape[0], ci, co, K, g, tbl, weight, out)
+        return out
+
+    def spconv_wgrad(self, G, D, tbl, shape, swap):
+        """dW (C_out, K, C_in) = sum_r G[tbl[r, k]]^T D[r] (swap: G is the output gradient, D the input)."""
+        rows, K = tbl.shape
+        ca, cb = G.shape[1], D.shape[1]
+        require_current_device(G, D, tbl)
+        dw = self._new(G, tuple(shape), torch.float32)
+        if rows == 0:
+            return dw.zero_()
+        ws = self._new(G, (int(self.lib.pdf_spconv_wgrad_ws_floats(rows, K, ca, cb)),), torch.float32)
+        self._call("spconv_wgrad", rows, G.shape[0], K, ca, cb, G, D, tbl, int(bool(swap)), ws, dw)
+        return dw
+
+    def spconv_colsum(self, g):
+        rows, c = g.shape
+        require_current_device(g)
+        out = self._new(g, (c,), torch.float32)
+        ws = self._new(g, (int(self.lib.pdf_spconv_colsum_ws_floats(c)),), torch.float32)
+        self._call("spconv_colsum", rows, c, g, ws, out)
         return out
 
     # -- batched test-time fragments (csrc/fragments.hip; pointcloudpdf_amd/testing.py drives them) ------------------------------------

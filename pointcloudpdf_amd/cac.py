@@ -31,7 +31,7 @@ Choices of this package where the reference leaves the result open:
 * ``eps > 0`` in the distillation loss runs as the composition (no reference recipe sets it).
 
 Not provided: open-set scoring over CAC (``engine.build_open_seg_step`` refuses the model: its ``backbone`` hook would hand features,
-not logits, to ``MaxProbability``) and the ``*-spunet`` CAC recipes (they need spconv)."""
+not logits, to ``MaxProbability``).  The ``*-spunet`` CAC recipes build over sparse_unet.py's SpUNet-v1m1."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
