@@ -15,7 +15,8 @@
  *     ABI 4 the reduced-precision mode of the Linear products is a per-call argument, `mma_input` below).  The only process-wide inputs
  *     are a few read-only PDFOPS_* environment variables that select kernel variants / grid caps for experiments and tests
  *     (PDFOPS_KNN_*, PDFOPS_PT_BLOCKS_*, PDFOPS_PT_CAP_<pass>; defaults are the measured best), read once per process, and
- *     PDFOPS_FPS_KERNEL (single | multi | mw8 | mw16: the kernel of the bucketed FPS), read at every launch;
+ *     PDFOPS_FPS_KERNEL (single | multi | mw8 | mw16: the kernel of the bucketed FPS) and PDFOPS_RL_FORM (auto | slab | group: the form
+ *     of the streaming Linear kernels at K >= 128, bit-identical results), read at every launch;
  *   - float data is fp32, indices/offsets are int32, `offset` arrays hold CUMULATIVE scene ends;
  *   - kNN placeholder for scenes with fewer than `nsample` points: idx = -1, dist2 = 1e10;
  *   - outputs written by plain stores need no initialisation (grouping/subtraction/

@@ -28,6 +28,7 @@
 #include "pdfops_common.h"
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 namespace rl2 {
 
@@ -248,6 +249,170 @@ __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
     }
 }
 
+// The group form of k_fwd, for launches with few row tiles and many column blocks (levels 3-5: the three-output q / k / v product, the
+// three-input dX = sum G_i W_i, the c x c products with statistics).  Same row blocks, same tile-to-wave assignment, same products in the
+// same order per output element (input, j, c: one accumulator chain) and the same epilogue as k_fwd -- bit-identical results and partial
+// rows -- but a workgroup owns GN 16-column blocks instead of one slab of NOB:
+//   - their weight fragments sit in LDS (dynamic, NIN x GN x K x 16 operands), filled once per workgroup by all four waves, instead of
+//     once per wave in registers.  The image is in fragment order, [input][block][j][lane]: lane l of the read for (block, j) takes the
+//     16 bytes at l, so a ds_read_b128 is contiguous over the wave (conflict-free without padding) and yields the A operands of the four
+//     products of one step.  Reduced-precision operands are rounded once, at the fill (8 bytes per lane and step);
+//   - a wave reads its row tile once per GN blocks and applies the prologue once: GN accumulators are live, the inputs are walked
+//     outermost, rows arrive in double-buffered batches of XB steps.
+// Nothing passes between waves through LDS except the fill (one barrier before the first tile) and the statistics sums (as in k_fwd).
+//
+// GROUP_GN, the 16-column blocks per workgroup.  Measured at 12,496 x 128, 3,124 x 256 and 780 x 512 (profiles/rowlin_group_probe.txt): two blocks beat four on
+// every launch -- 16 / 32 / 64 KB of fp32 fragments per input leave several workgroups per CU, and the grid keeps twice the waves.
+constexpr int GROUP_GN = 2;
+template <int K, int GN, int NIN, int MP> constexpr int group_lds_bytes() { return NIN * GN * (K / 16) * 64 * (int)sizeof(typename Mma<MP>::frag); }
+
+template <int K, int GN, int NIN, bool PRE, int ST, int MP>
+__global__ __launch_bounds__(256, 2) void k_fwd_group(FwdArgs a) {   // (at least two waves per SIMD: the images of 16-96 KB leave room for two workgroups per CU)
+    typedef typename Mma<MP>::frag wfrag;
+    constexpr bool STATS = ST != 0;
+    constexpr int NJ = K / 16;
+    static_assert(K >= 128 && NJ % 8 == 0 && (NIN == 1 || NIN == 3), "group form: K = 128 / 256 / 512, one or three inputs");
+    extern __shared__ __attribute__((aligned(16))) unsigned char group_lds[];
+    wfrag *Wl = reinterpret_cast<wfrag *>(group_lds);   // [NIN][GN][NJ][64]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    if (ST == 1 && a.ho_gran && blockIdx.x == 0 && blockIdx.y == 0) pdf_handoff_zero(a.ho_gran, a.O, a.ho_sync);
+    const int gcol0 = blockIdx.y * GN * 16;
+    int outi[GN], colb[GN];
+#pragma unroll
+    for (int ob = 0; ob < GN; ++ob) { outi[ob] = (gcol0 + ob * 16) / a.O; colb[ob] = gcol0 + ob * 16 - outi[ob] * a.O; }
+    {   // fill: fragment f = (input, block, j) goes to wave f & 3; all of a wave's global loads are in flight before its first LDS store
+        constexpr int PER_WAVE = NIN * GN * NJ / 4;   // 4 .. 24 fragments, one float4 per lane each
+        f32x4 w4[PER_WAVE];
+#pragma unroll
+        for (int t = 0; t < PER_WAVE; ++t) {
+            const int f = t * 4 + wave;
+            const int j = f % NJ, ob = (f / NJ) % GN, in = f / (NJ * GN);
+            const int col = gcol0 + ob * 16, oi = col / a.O;
+            const float *W = a.W[NIN > 1 ? in : oi];
+            const long o = col - oi * a.O + li;
+            if (a.wsk == 1) {
+                w4[t] = *reinterpret_cast<const f32x4 *>(W + o * a.wso + 16 * j + 4 * kq);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) w4[t][c] = W[o * a.wso + (long)(16 * j + 4 * kq + c) * a.wsk];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < PER_WAVE; ++t) Wl[(t * 4 + wave) * 64 + lane] = Mma<MP>::cvt(w4[t]);
+    }
+    __shared__ float bco[ST == 2 ? 3 : 1][GN * 16];   // scale | shift | mean of this workgroup's columns (ST == 2)
+    if (ST == 2 && threadIdx.x < 3 * GN * 16) {
+        const int v = threadIdx.x / (GN * 16), t = threadIdx.x % (GN * 16);
+        bco[ST == 2 ? v : 0][t] = a.bcoef[(long)v * a.O + gcol0 + t];
+    }
+    __shared__ float pco[PRE ? 2 : 1][PRE ? K : 1];
+    if (PRE)
+        for (int t = threadIdx.x; t < K; t += 256) { pco[0][t] = a.scale[t]; pco[PRE ? 1 : 0][t] = a.shift[t]; }
+    __syncthreads();   // the weight image, bco and pco are complete before any wave's first tile
+    f32x4 s4[STATS ? GN : 1], ss4[STATS ? GN : 1];
+    if (STATS) {
+#pragma unroll
+        for (int ob = 0; ob < GN; ++ob) { s4[ob] = f32x4{0.f, 0.f, 0.f, 0.f}; ss4[ob] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    }
+    const float relu_lo = a.relu ? 0.f : -INFINITY;
+    constexpr int XB = 8, NBJ = NJ / XB, NB = NIN * NBJ;   // batches of XB steps; batch b + 1 is in flight while batch b is multiplied
+    const long ntiles = (a.N + 15) / 16;
+    for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
+        const long n = tile * 16 + li;
+        const bool valid = n < a.N;
+        const long row = valid ? n : 0;   // (rows past the end read row 0 and never store)
+        f32x4 acc[GN];
+#pragma unroll
+        for (int ob = 0; ob < GN; ++ob) acc[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 xb[2][XB];
+#pragma unroll
+        for (int t = 0; t < XB; ++t) xb[0][t] = *reinterpret_cast<const f32x4 *>(a.X[0] + row * a.ldx + 4 * kq + 16 * t);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (b + 1 < NB) {
+                const float *xr = a.X[(b + 1) / NBJ] + row * a.ldx + 4 * kq + 16 * ((b + 1) % NBJ) * XB;
+#pragma unroll
+                for (int t = 0; t < XB; ++t) xb[(b + 1) & 1][t] = *reinterpret_cast<const f32x4 *>(xr + 16 * t);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const int in = b / NBJ;
+#pragma unroll
+            for (int t = 0; t < XB; ++t) {
+                const int j = (b % NBJ) * XB + t;
+                f32x4 x4 = xb[b & 1][t];
+                if (PRE) {
+                    const f32x4 sc = *reinterpret_cast<const f32x4 *>(&pco[0][16 * j + 4 * kq]);
+                    const f32x4 sh = *reinterpret_cast<const f32x4 *>(&pco[PRE ? 1 : 0][16 * j + 4 * kq]);
+                    x4 = x4 * sc + sh;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) x4[c] = fmaxf(x4[c], relu_lo);
+                }
+                wfrag wa[GN];
+#pragma unroll
+                for (int ob = 0; ob < GN; ++ob) wa[ob] = Wl[((in * GN + ob) * NJ + j) * 64 + lane];
+                if constexpr (MP == 0) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+#pragma unroll
+                        for (int ob = 0; ob < GN; ++ob)
+                            acc[ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[ob][c], x4[c], acc[ob], 0, 0, 0);
+                } else {
+                    const wfrag xh = Mma<MP>::cvt(x4);
+#pragma unroll
+                    for (int ob = 0; ob < GN; ++ob) acc[ob] = Mma<MP>::mma(wa[ob], xh, acc[ob]);
+                }
+            }
+        }
+#pragma unroll
+        for (int ob = 0; ob < GN; ++ob) {
+            f32x4 v = acc[ob];
+            if (a.roww) v *= a.roww[row * a.rws];
+            const float *bp = a.bias[NIN > 1 ? 0 : outi[ob]];
+            f32x4 bias4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bias4[r] = bp ? bp[colb[ob] + 4 * kq + r] : 0.f;
+            v += bias4;
+            float *dst = a.Y[outi[ob]] + row * a.ldy + colb[ob] + 4 * kq;
+            if (a.accumulate && valid) v += *reinterpret_cast<const f32x4 *>(dst);
+            if (valid) *reinterpret_cast<f32x4 *>(dst) = v;
+            if (ST == 1 && valid) { s4[ob] += v; ss4[ob] += v * v; }
+            if (ST == 2) {
+                const f32x4 x4 = *reinterpret_cast<const f32x4 *>(a.bx + row * a.ldb + colb[ob] + 4 * kq);
+                const f32x4 sc = *reinterpret_cast<const f32x4 *>(&bco[0][ob * 16 + 4 * kq]);
+                const f32x4 sh = *reinterpret_cast<const f32x4 *>(&bco[ST == 2 ? 1 : 0][ob * 16 + 4 * kq]);
+                const f32x4 mu = *reinterpret_cast<const f32x4 *>(&bco[ST == 2 ? 2 : 0][ob * 16 + 4 * kq]);
+                const f32x4 pre = x4 * sc + sh;
+                f32x4 gm;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) gm[c] = (valid && (!a.brelu || pre[c] > 0.f)) ? v[c] : 0.f;
+                s4[ob] += gm;
+                ss4[ob] += gm * (x4 - mu);
+            }
+        }
+    }
+    if (STATS) {
+        __shared__ float red[4][2][GN * 16];
+#pragma unroll
+        for (int ob = 0; ob < GN; ++ob)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float s = s4[ob][r], ss = ss4[ob][r];
+#pragma unroll
+                for (int m = 1; m < 16; m <<= 1) { s += __shfl_xor(s, m, 64); ss += __shfl_xor(ss, m, 64); }
+                if (li == 0) { red[wave][0][ob * 16 + 4 * kq + r] = s; red[wave][1][ob * 16 + 4 * kq + r] = ss; }
+            }
+        __syncthreads();
+        const int t = threadIdx.x;
+        if (t < GN * 16) {
+            float *prow = a.partial + (size_t)blockIdx.x * 2 * a.O;
+            prow[gcol0 + t] = red[0][0][t] + red[1][0][t] + red[2][0][t] + red[3][0][t];
+            const float ss = red[0][1][t] + red[1][1][t] + red[2][1][t] + red[3][1][t];
+            prow[a.O + gcol0 + t] = ST == 2 ? ss * a.bcoef[3 * (long)a.O + gcol0 + t] : ss;
+        }
+    }
+}
+
 constexpr int WG_MAXG = 5;   // weight gradients of one launch (blockIdx.z): q / k / v of one input, or the five c x c products of a Bottleneck
 struct WArgs {
     long N;
@@ -463,6 +628,43 @@ long wgrad_ws_floats(long n, int k, int o, int ng) {
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// Which form a launch takes (K >= 128, one or three inputs; `blocks` 16-column blocks).  PDFOPS_RL_FORM = auto | slab | group, read at
+// every launch (a test drives both forms inside one process), forces a form wherever the group form supports the shape.  auto is the
+// measured rule: at the row counts of levels 3-5 (12,496 x 128, 3,124 x 256, 780 x 512) every launch beat the slab form by more than its
+// spread except the three-output product at K = 128 (28.2 against 29.0 us, spread 0.6-0.9: past its bound by 0.1-0.3 us in two probe runs,
+// short of it in a third -- not told from noise), which stays on the slab form (profiles/rowlin_group_probe.txt);
+// nothing larger was measured, and there a wave has enough tiles to amortise its fragments.
+constexpr long GROUP_MAX_ROWS = 16384;
+static bool group_form_wanted(const FwdArgs &a, int k, int blocks) {
+    if (blocks % GROUP_GN) return false;
+    if (const char *f = getenv("PDFOPS_RL_FORM")) {
+        if (!strcmp(f, "slab")) return false;
+        if (!strcmp(f, "group")) return true;
+    }
+    return a.N <= GROUP_MAX_ROWS && !(k == 128 && blocks * 16 > a.O);
+}
+
+template <int K, int GN, int NIN, bool PRE, int ST, int MP>
+static bool launch_group_kernel(const FwdArgs &a, dim3 grid, hipStream_t s) {
+    constexpr int lds = group_lds_bytes<K, GN, NIN, MP>();
+    static PdfLdsLimit site;
+    if (!pdf_lds_limit_raised(site, reinterpret_cast<const void *>(&k_fwd_group<K, GN, NIN, PRE, ST, MP>), lds)) return false;
+    k_fwd_group<K, GN, NIN, PRE, ST, MP><<<grid, 256, lds, s>>>(a);
+    return true;
+}
+
+// false: the dynamic LDS limit was refused, the caller launches the slab form
+template <int K, int GN, int NIN, int MP>
+static bool launch_fwd_group(const FwdArgs &a, int blocks, int gx, hipStream_t s) {
+    const bool pre = a.scale != nullptr, stats = a.partial != nullptr, bst = stats && a.bx != nullptr;
+    const dim3 grid((unsigned)gx, (unsigned)(blocks / GN));
+    if (bst) return launch_group_kernel<K, GN, NIN, false, 2, MP>(a, grid, s);
+    if constexpr (NIN == 1) {
+        if (stats) return pre ? launch_group_kernel<K, GN, 1, true, 1, MP>(a, grid, s) : launch_group_kernel<K, GN, 1, false, 1, MP>(a, grid, s);
+    }
+    return pre ? launch_group_kernel<K, GN, NIN, true, 0, MP>(a, grid, s) : launch_group_kernel<K, GN, NIN, false, 0, MP>(a, grid, s);
+}
+
 template <int K, int NOB, int NIN, int MP>
 static int launch_fwd(const FwdArgs &a, int nslabs, hipStream_t s) {   // returns the number of row blocks (= partial rows written)
     const bool pre = a.scale != nullptr, stats = a.partial != nullptr, bst = stats && a.bx != nullptr;
@@ -475,6 +677,9 @@ static int launch_fwd(const FwdArgs &a, int nslabs, hipStream_t s) {   // return
     static const int total = [] { const char *v = getenv("PDFOPS_RL_BLOCKS"); const int x = v ? atoi(v) : 0; return x > 0 ? x : 512; }();
     int gx = fwd_row_blocks(a.N);
     if (!stats || bst) gx = std::max(1, std::min(gx, std::max(8, total / std::max(nslabs, 1))));   // (bst: the caller is told the row count)
+    if constexpr (K >= 128 && NIN != 2) {
+        if (group_form_wanted(a, K, nslabs * NOB) && launch_fwd_group<K, GROUP_GN, NIN, MP>(a, nslabs * NOB, gx, s)) return gx;
+    }
     const dim3 grid((unsigned)gx, (unsigned)nslabs);
     if (bst) {   // BatchNorm-backward sums of the output (dgrad kernels: no input prologue)
         k_fwd<K, NOB, NIN, false, 2, MP><<<grid, 256, 0, s>>>(a);
