@@ -51,8 +51,9 @@ extern "C" {
  * 13 = pdf_criteria_workspace_floats / pdf_ce_ex_* / pdf_focal_* / pdf_dice_* / pdf_bfocal_* added (no existing parameter list changed);
  * 14 = pdf_grid_pool_* / pdf_grid_unpool_forward / pdf_gva_* added (no existing parameter list changed);
  * 15 = pdf_cac_* added (no existing parameter list changed);
- * 16 = pdf_spconv_* added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 16
+ * 16 = pdf_spconv_* added (no existing parameter list changed);
+ * 17 = pdf_serial_* added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 17
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -944,6 +945,37 @@ int pdf_gva_attend_forward(long n, long nv, int s, int c, int groups, const floa
 int pdf_gva_attend_backward(long n, long nv, int s, int c, int groups, const float *g_out, const float *p, const float *value,
                             const float *peb, const int *idx, const int *inv_off, const int *inv_entry, float *g_logits, float *g_value,
                             float *g_peb, void *stream);
+
+/* ---- PointTransformer-V3 (point_transformer_v3m1_base.py): serialization, code-shift pooling partition (csrc/serialization.hip) and
+ * the patch attention over serialized order (csrc/serial_attention.hip).
+ * pdf_serial_codes: code (k, n) int64, row j = batch << 3 depth | curve_j(grid_coord & (2^depth - 1)); the curve of row j is the 4-bit
+ *   field j of `orders`: 0 z, 1 z-trans (x and y swapped), 2 hilbert, 3 hilbert-trans -- bit-identical to
+ *   models/utils/serialization/{z_order,hilbert}.py (Skilling's transform per lane, no table).  1 <= k <= 8, 0 <= depth <= 16.
+ * pdf_serial_sort: order (k, n) int64 = stable ascending order of every code row (two stable 32-bit radix sorts, low word first; equal
+ *   codes keep row order), inverse (k, n) int64 with inverse[j, order[j, i]] = i.  workspace: pdf_serial_workspace_bytes(n), 256-byte aligned.
+ * pdf_serial_pool_partition (SerializedPooling :384-396): key = code0[order0[i]] >> shift is ascending in i, so one flag + scan pass gives
+ *   cluster (n) int64 = rank of the row's key among the distinct keys, idx_ptr (count + 1 of n + 1 written) int32, sorted (n) int32 = the rows
+ *   cluster by cluster in ASCENDING ROW INDEX inside a cluster (what a stable sort of cluster yields), head (count of n written) int64 = the
+ *   first of them, count (1) int32.  Same workspace.
+ * pdf_serial_attn_*: qkv (n, 3 c) fp32 rows in original order [q | k | v], head h' = columns 16 h' .. 16 h' + 15 of each third; order (n)
+ *   int64 = the serialized order; qtab (nq, 4) int32 {q_start, q_len <= 64, k_start, k_len}: the queries at serialized positions
+ *   [q_start, q_start + q_len) attend to the keys at [k_start, k_start + k_len); ktab (nk, 8) int32 {k_start, k_len <= 64, qa_start, qa_len,
+ *   qb_start, qb_len, shared_from, 0}: the keys of the chunk receive the queries of window a, then those of window b for the keys at
+ *   positions >= shared_from (fixed order, no float atomics).  The q windows and the key chunks each partition [0, n): every element of
+ *   out (n, c), lse (n, h, 2), delta (n, h) and g_qkv (n, 3 c) is written exactly once.  out = softmax(scale q k^T) v per head in fp32 on
+ *   v_mfma_f32_16x16x4_f32 with an online softmax; lse = the row's log-sum-exp as the pair (m, l): row maximum and sum of exp(s - m).  Shapes outside pdf_serial_attn_supported (c == 16 h,
+ *   c <= 512, k >= 1): PDF_ERR_UNSUPPORTED.  A table row that points outside [0, n) is skipped. */
+int pdf_serial_attn_supported(int c, int h, int k);
+long pdf_serial_workspace_bytes(long n);
+int pdf_serial_codes(long n, int k, int orders, int depth, const int *grid_coord, const long long *batch, long long *code, void *stream);
+int pdf_serial_sort(long n, int k, const long long *code, long long *order, long long *inverse, void *workspace, void *stream);
+int pdf_serial_pool_partition(long n, int shift, const long long *code0, const long long *order0, long long *cluster, int *sorted,
+                              int *idx_ptr, long long *head, int *count, void *workspace, void *stream);
+int pdf_serial_attn_forward(long n, int c, int h, float scale, const float *qkv, const long long *order, const int *qtab, int nq,
+                            float *out, float *lse, void *stream);
+int pdf_serial_attn_backward(long n, int c, int h, float scale, const float *qkv, const float *out, const float *lse, const float *g_out,
+                             const long long *order, const int *qtab, int nq, const int *ktab, int nk, float *delta, float *g_qkv,
+                             void *stream);
 
 #ifdef __cplusplus
 }

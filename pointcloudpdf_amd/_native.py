@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 16   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 17   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -159,6 +159,12 @@ _HIP_ONLY_PROTOS = {
     "spconv_small_dgrad": "liiipppp",
     "spconv_wgrad": "lliiipppipp",
     "spconv_colsum": "lippp",
+    # csrc/serialization.hip, csrc/serial_attention.hip
+    "serial_codes": "liiippp",
+    "serial_sort": "lipppp",
+    "serial_pool_partition": "lipppppppp",
+    "serial_attn_forward": "liifpppipp",
+    "serial_attn_backward": "liifppppppipipp",
 }
 _KIND = {"i": c_int, "l": c_long, "f": c_float, "d": c_double, "p": c_void_p}
 
@@ -722,6 +728,10 @@ class HipBackend(CBackend):
         lib.pdf_cac_distill_workspace_floats.argtypes = [c_int]
         lib.pdf_spconv_supported.restype = c_int
         lib.pdf_spconv_supported.argtypes = [c_int, c_int, c_int]
+        lib.pdf_serial_attn_supported.restype = c_int
+        lib.pdf_serial_attn_supported.argtypes = [c_int, c_int, c_int]
+        lib.pdf_serial_workspace_bytes.restype = c_long
+        lib.pdf_serial_workspace_bytes.argtypes = [c_long]
         lib.pdf_spconv_geometry_workspace_bytes.restype = c_long
         lib.pdf_spconv_geometry_workspace_bytes.argtypes = [c_long]
         lib.pdf_spconv_bucket_rows.restype = c_long
@@ -2431,6 +2441,67 @@ class HipBackend(CBackend):
             raise PdfOpsError("gva_attend_backward: inverse table with a non-zero entry base")
         self._call("gva_attend_backward", int(n), nv, int(s), c, groups, g_out, p, value, peb, idx, off, ent, gl, gv, gp)
         return gl, gv, gp
+
+    # ---- PointTransformer-V3: serialization, pooling partition, patch attention (csrc/serialization.hip, csrc/serial_attention.hip) ----
+    SERIAL_ORDERS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
+
+    def serial_attn_supported(self, c, h, k):
+        return bool(self.lib.pdf_serial_attn_supported(int(c), int(h), int(k)))
+
+    def _serial_ws(self, n, device):
+        return torch.empty(int(self.lib.pdf_serial_workspace_bytes(n)), dtype=torch.uint8, device=device)
+
+    def serial_codes(self, grid_coord, batch, depth, orders):
+        """grid_coord (n, 3) int32, batch (n) int64 -> code (k, n) int64, one row per curve name in ``orders``."""
+        _check(grid_coord, torch.int32, "grid_coord"); _check(batch, torch.int64, "batch")
+        n, k = int(grid_coord.shape[0]), len(orders)
+        if not 1 <= k <= 8:
+            raise ValueError("serial_codes: 1 to 8 orders")
+        packed = 0
+        for j, o in enumerate(orders):
+            packed |= self.SERIAL_ORDERS[o] << (4 * j)
+        code = torch.empty((k, n), dtype=torch.int64, device=grid_coord.device)
+        self._call("serial_codes", n, k, packed, int(depth), grid_coord, batch, code)
+        return code
+
+    def serial_sort(self, code):
+        """code (k, n) int64 (non-negative) -> (order, inverse), both (k, n) int64; equal codes keep row order."""
+        _check(code, torch.int64, "code")
+        k, n = code.shape
+        order, inverse = torch.empty_like(code), torch.empty_like(code)
+        if n:
+            self._call("serial_sort", int(n), int(k), code, order, inverse, self._serial_ws(int(n), code.device))
+        return order, inverse
+
+    def serial_pool_partition(self, code0, order0, shift):
+        """-> (cluster (n) int64, sorted (n) int32, idx_ptr (m + 1) int32, head (m) int64, m).  One host read: the cluster count."""
+        _check(code0, torch.int64, "code"); _check(order0, torch.int64, "order")
+        n, dev = int(code0.shape[0]), code0.device
+        cluster = torch.empty(n, dtype=torch.int64, device=dev)
+        srt = torch.empty(n, dtype=torch.int32, device=dev)
+        idx_ptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        head = torch.empty(n, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        self._call("serial_pool_partition", n, int(shift), code0, order0, cluster, srt, idx_ptr, head, count, self._serial_ws(n, dev))
+        m = int(count.item())
+        return cluster, srt, idx_ptr[:m + 1], head[:m], m
+
+    def serial_attn_forward(self, qkv, order, qtab, h, scale):
+        _check(qkv, torch.float32, "qkv"); _check(order, torch.int64, "order"); _check(qtab, torch.int32, "qtab")
+        n, c = int(qkv.shape[0]), int(qkv.shape[1]) // 3
+        out = torch.empty((n, c), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((n, h, 2), dtype=torch.float32, device=qkv.device)   # (row maximum, sum of exp(s - maximum))
+        self._call("serial_attn_forward", n, c, int(h), float(scale), qkv, order, qtab, int(qtab.shape[0]), out, lse)
+        return out, lse
+
+    def serial_attn_backward(self, qkv, out, lse, g_out, order, qtab, ktab, h, scale):
+        _check(g_out, torch.float32, "g_out"); _check(ktab, torch.int32, "ktab")
+        n, c = int(qkv.shape[0]), int(qkv.shape[1]) // 3
+        delta = torch.empty((n, h), dtype=torch.float32, device=qkv.device)
+        g_qkv = torch.empty_like(qkv)
+        self._call("serial_attn_backward", n, c, int(h), float(scale), qkv, out, lse, g_out, order, qtab, int(qtab.shape[0]), ktab,
+                   int(ktab.shape[0]), delta, g_qkv)
+        return g_qkv
 
 
 _lock = threading.Lock()

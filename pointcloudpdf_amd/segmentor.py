@@ -161,3 +161,27 @@ class DefaultSegmentor(nn.Module):
         if "segment" in input_dict.keys():
             return dict(loss=self.criteria(seg_logits, input_dict["segment"]), seg_logits=seg_logits)
         return dict(seg_logits=seg_logits)
+
+
+@MODELS.register_module()
+class DefaultSegmentorV2(nn.Module):
+    """default.py:65-97: a backbone that returns a ``Point`` (PT-v3m1) and a Linear head over its features."""
+
+    def __init__(self, num_classes, backbone_out_channels, backbone=None, criteria=None):
+        super().__init__()
+        self.seg_head = nn.Linear(backbone_out_channels, num_classes) if num_classes > 0 else nn.Identity()
+        self.backbone = build_model(backbone)
+        self.criteria = build_criteria(criteria)
+
+    @dense.fp32_path
+    def forward(self, input_dict):
+        from .point_transformer_v3 import Point, _apply
+
+        point = Point(input_dict)
+        point = self.backbone(point)
+        seg_logits = _apply(self.seg_head, point.feat)
+        if self.training:
+            return dict(loss=self.criteria(seg_logits, input_dict["segment"]))
+        if "segment" in input_dict.keys():
+            return dict(loss=self.criteria(seg_logits, input_dict["segment"]), seg_logits=seg_logits)
+        return dict(seg_logits=seg_logits)
