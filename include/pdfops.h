@@ -36,6 +36,7 @@ extern "C" {
 #define PDF_ERR_BAD_ARG (-1)      /* null pointer / negative size */
 #define PDF_ERR_NSAMPLE (-2)      /* nsample outside 1..128 (reference: best_dist[128], knn_query_cuda_kernel.cu:82) */
 #define PDF_ERR_UNSUPPORTED (-3)  /* shape outside what the kernels are built for */
+#define PDF_ERR_NOT_CONVERGED (-4) /* an iteration with a proven bound on its rounds ran past it (pdf_pg_cluster_labels) */
 
 /* ABI version of THIS header.  pdf_abi_version() returns the version the loaded library was built with: a caller built against another
  * version must refuse to call (parameter lists differ; pointcloudpdf_amd/_native.py does).  History: 1 = rounds 1-3 (signatures changed
@@ -52,8 +53,9 @@ extern "C" {
  * 14 = pdf_grid_pool_* / pdf_grid_unpool_forward / pdf_gva_* added (no existing parameter list changed);
  * 15 = pdf_cac_* added (no existing parameter list changed);
  * 16 = pdf_spconv_* added (no existing parameter list changed);
- * 17 = pdf_serial_* added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 17
+ * 17 = pdf_serial_* added (no existing parameter list changed);
+ * 18 = pdf_pg_* and PDF_ERR_NOT_CONVERGED added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 18
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -976,6 +978,48 @@ int pdf_serial_attn_forward(long n, int c, int h, float scale, const float *qkv,
 int pdf_serial_attn_backward(long n, int c, int h, float scale, const float *qkv, const float *out, const float *lse, const float *g_out,
                              const long long *order, const int *qtab, int nq, const int *ktab, int nk, float *delta, float *g_qkv,
                              void *stream);
+
+/* ---- PointGroup (PG-v1m1: libs/pointgroup_ops, point_group_v1m1_base.py, InsSegEvaluator): csrc/point_group.hip.
+ * Ball table (ballquery_batch_p as CSR): row q = the points of q's scene in ASCENDING index with d2 < radius^2 (strict; fp32, the as-written
+ *   expression of the reference, the arithmetic of pdf_dist_fma_mode()), cut after the first 1,000.  offset (b) = scene ends, b <= 64
+ *   (else PDF_ERR_UNSUPPORTED).  pdf_pg_ball_count writes start_len (n, 2) int32 = {exclusive scan of the row lengths in row order, length}
+ *   and total (1) int64 on the device; the caller reads total, allocates idx (total) and calls pdf_pg_ball_fill with the SAME, untouched
+ *   workspace (pdf_pg_ball_workspace_bytes(n, b), 256-byte aligned).  total >= 2^31: PDF_ERR_UNSUPPORTED (start_len is int32, as upstream).
+ * Clustering (bfs_cluster): pdf_pg_cluster_labels runs directed min-label propagation over the equal-label edges to its fixed point
+ *   (rounds in batches, one host read per batch, at most n + 1 rounds, else PDF_ERR_NOT_CONVERGED; synchronises the stream) and reads the
+ *   clusters off: L (n) = smallest index that reaches the point, size (n) = class sizes at the roots, rank (n) = cluster number of a kept
+ *   root (size >= threshold; ascending root index) or -1, offs (n + 1, count + 1 written) = cluster offsets, code (n) int64 = the point's
+ *   cluster number or n, info (3) int64 = {clusters, points in clusters, rounds}, counters (64) = scratch.  The caller sorts `code` stably
+ *   (pdf_serial_sort) and pdf_pg_cluster_fill writes cluster_idxs (s, 2) int32 = {cluster, point}: members in ascending index.
+ * Proposals (point_group_v1m1_base.py:140-170): pdf_pg_proposals_select keeps the clusters with more than propose_points members: rank (nc) =
+ *   proposal number or -1, new_offs (kept + 1 written), info (2) int64 = {kept, their members}; pdf_pg_proposals_fill writes, per kept cluster
+ *   (cluster_idxs (ns, 2); a cluster whose offsets leave it is skipped),
+ *   members (object_idxs[member], or the member itself with object_idxs == NULL; int32 indices into the npts points), prop_of[member] = proposal,
+ *   classes (int64) = label[first member], scores = mean over the members of prob[member, class] (prob (npts, k) fp32; double accumulator,
+ *   fixed order), and masks (kept, npts) int32 = 1 at the members when masks != NULL (zeroed by the caller, as prop_of is set to -1).
+ * pdf_pg_intersections: for the m evaluated points j with p = prop_of[map ? map[j] : j] >= 0: table[p, slot[j]] += 1 (table (np, g), slots
+ *   outside [0, g) skipped), vert[p] += 1, voidc[p] += isvoid[j] (bytes); integer atomics, outputs zeroed by the caller.
+ * Bias losses (:74-86): loss (2) = {bias_l1_loss, bias_cosine_loss} in fp32, or in double with a float64 centroid (centroid_f64 != 0); d1, d2
+ *   (n, 3) fp32 = the unscaled gradients of the two terms, acc = pdf_pg_bias_loss_workspace_doubles() doubles (nothing to zero; acc[0] = 1 /
+ *   denominator).  Backward: grad = (d1 gy[0] + d2 gy[1]) acc[0], gy (2) of the loss' type.  Capturable: no host read, no memset, no atomics. */
+long pdf_pg_ball_workspace_bytes(int n, int b);
+int pdf_pg_ball_count(int n, int b, float radius, const float *xyz, const int *offset, int *start_len, long long *total, void *workspace,
+                      long workspace_bytes, void *stream);
+int pdf_pg_ball_fill(int n, int b, float radius, const float *xyz, const int *offset, const int *start_len, long total, int *idx,
+                     void *workspace, long workspace_bytes, void *stream);
+int pdf_pg_cluster_labels(int n, const int *label, const int *idx, long total, const int *start_len, int threshold, int *L, int *size, int *rank,
+                          int *offs, long long *code, long long *info, unsigned *counters, void *stream);
+int pdf_pg_cluster_fill(long n, long s, const long long *code, const long long *order, int *cluster_idxs, void *stream);
+int pdf_pg_proposals_select(int nc, const int *offs, int propose_points, int *rank, int *new_offs, long long *info, void *stream);
+int pdf_pg_proposals_fill(int nc, long npts, int k, long ns, const int *cluster_idxs, const int *offs, const int *rank, const int *new_offs,
+                          const int *label, long nobj, const long long *object_idxs, const float *prob, int *members, int *prop_of,
+                          long long *classes, float *scores, int *masks, void *stream);
+int pdf_pg_intersections(long m, long nsrc, int np, int g, const int *prop_of, const long long *map, const int *slot,
+                         const unsigned char *isvoid, int *table, int *vert, int *voidc, void *stream);
+long pdf_pg_bias_loss_workspace_doubles(void);
+int pdf_pg_bias_loss_forward(long n, const float *pred, const float *coord, const void *centroid, int centroid_f64, const long long *instance,
+                             long long ignore, float *d1, float *d2, double *acc, void *loss, void *stream);
+int pdf_pg_bias_loss_backward(long n, const float *d1, const float *d2, const double *acc, const void *gy, int f64, float *grad, void *stream);
 
 #ifdef __cplusplus
 }

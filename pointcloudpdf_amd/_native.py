@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 17   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 18   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -165,6 +165,16 @@ _HIP_ONLY_PROTOS = {
     "serial_pool_partition": "lipppppppp",
     "serial_attn_forward": "liifpppipp",
     "serial_attn_backward": "liifppppppipipp",
+    # csrc/point_group.hip
+    "pg_ball_count": "iifpppppl",
+    "pg_ball_fill": "iifppplppl",
+    "pg_cluster_labels": "ipplpi" + "p" * 7,
+    "pg_cluster_fill": "llppp",
+    "pg_proposals_select": "ipippp",
+    "pg_proposals_fill": "ililpppppl" + "p" * 7,
+    "pg_intersections": "llii" + "p" * 7,
+    "pg_bias_loss_forward": "lpppiplpppp",
+    "pg_bias_loss_backward": "lppppip",
 }
 _KIND = {"i": c_int, "l": c_long, "f": c_float, "d": c_double, "p": c_void_p}
 
@@ -689,6 +699,10 @@ class HipBackend(CBackend):
         lib.pdf_fragment_bounds_ws_doubles.argtypes = [c_int]
         lib.pdf_abi_version.restype = c_int
         lib.pdf_build_info.restype = ctypes.c_char_p
+        lib.pdf_pg_ball_workspace_bytes.restype = c_long
+        lib.pdf_pg_ball_workspace_bytes.argtypes = [c_int, c_int]
+        lib.pdf_pg_bias_loss_workspace_doubles.restype = c_long
+        lib.pdf_pg_bias_loss_workspace_doubles.argtypes = []
         got = int(lib.pdf_abi_version())
         if got != ABI_VERSION:   # parameter lists differ between versions: calling through would hand shifted arguments to the kernels
             raise PdfOpsError(f"libpdfops ABI {got} != {ABI_VERSION} expected by pointcloudpdf_amd/_native.py (include/pdfops.h: PDF_ABI_VERSION): "
@@ -2502,6 +2516,113 @@ class HipBackend(CBackend):
         self._call("serial_attn_backward", n, c, int(h), float(scale), qkv, out, lse, g_out, order, qtab, int(qtab.shape[0]), ktab,
                    int(ktab.shape[0]), delta, g_qkv)
         return g_qkv
+
+    # ---- PointGroup: ball table, clustering, proposals, intersection table, bias losses (csrc/point_group.hip) ----
+    def pg_ball_table(self, coords, offset, radius):
+        """coords (n, 3) fp32, offset (b) int32 scene ends -> (idx (total) int32, start_len (n, 2) int32): ballquery_batch_p as CSR, rows in
+        ascending index, cut at 1,000.  One host read (the total)."""
+        _check(coords, torch.float32, "coords"); _check(offset, torch.int32, "offset")
+        n, b, dev = int(coords.shape[0]), int(offset.shape[0]), coords.device
+        start_len = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        if n == 0:
+            return torch.empty(0, dtype=torch.int32, device=dev), start_len
+        if not radius > 0:
+            raise ValueError("pg_ball_table: radius must be positive")
+        nbytes = int(self.lib.pdf_pg_ball_workspace_bytes(n, b))
+        if nbytes <= 0:
+            raise PdfOpsError(f"pg_ball_table: {b} scenes (1 to 64 supported)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        self._call("pg_ball_count", n, b, float(radius), coords, offset, start_len, total, ws, nbytes)
+        t = int(total.item())
+        if t >= 2 ** 31:
+            raise PdfOpsError(f"pg_ball_table: {t} table entries do not fit the int32 starts of start_len")
+        idx = torch.empty(t, dtype=torch.int32, device=dev)
+        self._call("pg_ball_fill", n, b, float(radius), coords, offset, start_len, t, idx, ws, nbytes)
+        return idx, start_len
+
+    def pg_cluster(self, label, idx, start_len, threshold, with_stats=False):
+        """bfs_cluster on the device -> (cluster_idxs (s, 2) int32, cluster_offsets (c + 1) int32); members in ascending index."""
+        _check(label, torch.int32, "semantic_label"); _check(idx, torch.int32, "ball_query_idxs"); _check(start_len, torch.int32, "start_len")
+        n, dev = int(start_len.shape[0]), label.device
+        if label.shape[0] != n:
+            raise ValueError("pg_cluster: one label per row of start_len")
+        if n == 0:
+            out = torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+            return out + ({"rounds": 0},) if with_stats else out
+        i32 = torch.empty((4, n + 1), dtype=torch.int32, device=dev)
+        code = torch.empty((1, n), dtype=torch.int64, device=dev)
+        info = torch.empty(3, dtype=torch.int64, device=dev)
+        counters = torch.empty(64, dtype=torch.int32, device=dev)
+        self._call("pg_cluster_labels", n, label, idx if idx.numel() else None, int(idx.numel()), start_len, int(threshold), i32[0], i32[1], i32[2], i32[3],
+                   code, info, counters)
+        c, s, rounds = (int(v) for v in info.tolist())
+        cluster_idxs = torch.empty((s, 2), dtype=torch.int32, device=dev)
+        if s:
+            order, _ = self.serial_sort(code)
+            self._call("pg_cluster_fill", n, s, code, order, cluster_idxs)
+        offsets = i32[3, :c + 1].clone()
+        return (cluster_idxs, offsets, {"rounds": rounds, "labels": i32[0, :n]}) if with_stats else (cluster_idxs, offsets)
+
+    def pg_proposals(self, cluster_idxs, cluster_offsets, label, object_idxs, prob, propose_points, want_masks=False):
+        """Lines 140-170 of point_group_v1m1_base.py on the compact clusters -> dict(offsets (p + 1) int32, members int32, proposal_of (npts)
+        int32, classes (p) int64, scores (p) fp32, masks (p, npts) int32 or None).  One host read (the counts)."""
+        _check(cluster_idxs, torch.int32, "cluster_idxs"); _check(cluster_offsets, torch.int32, "cluster_offsets"); _check(label, torch.int32, "label")
+        _check(prob, torch.float32, "prob")
+        if object_idxs is not None:
+            _check(object_idxs, torch.int64, "object_idxs")
+        nc, dev = int(cluster_offsets.shape[0]) - 1, prob.device
+        npts, k = int(prob.shape[0]), int(prob.shape[1])
+        rank = torch.empty(max(nc, 1), dtype=torch.int32, device=dev)
+        new_offs = torch.empty(nc + 1, dtype=torch.int32, device=dev)
+        info = torch.empty(2, dtype=torch.int64, device=dev)
+        self._call("pg_proposals_select", nc, cluster_offsets, int(propose_points), rank, new_offs, info)
+        p, s = (int(v) for v in info.tolist())
+        members = torch.empty(s, dtype=torch.int32, device=dev)
+        prop_of = torch.full((npts,), -1, dtype=torch.int32, device=dev)
+        classes = torch.empty(p, dtype=torch.int64, device=dev)
+        scores = torch.empty(p, dtype=torch.float32, device=dev)
+        masks = torch.zeros((p, npts), dtype=torch.int32, device=dev) if want_masks else None
+        if p:
+            self._call("pg_proposals_fill", nc, npts, k, int(cluster_idxs.shape[0]), cluster_idxs, cluster_offsets, rank, new_offs, label, int(label.shape[0]), object_idxs, prob,
+                       members, prop_of, classes, scores, masks)
+        return dict(offsets=new_offs[:p + 1].clone(), members=members, proposal_of=prop_of, classes=classes, scores=scores, masks=masks)
+
+    def pg_intersections(self, prop_of, nprop, slot, nslots, isvoid, index_map=None):
+        """-> (table (nprop, nslots), vert_count (nprop), void_intersection (nprop)), int32: the counts of associate_instances."""
+        _check(prop_of, torch.int32, "proposal_of"); _check(slot, torch.int32, "slot"); _check(isvoid, torch.bool, "void mask")
+        if index_map is not None:
+            _check(index_map, torch.int64, "index map")
+        dev, m = prop_of.device, int(slot.shape[0])
+        table = torch.zeros((nprop, nslots), dtype=torch.int32, device=dev)
+        vert = torch.zeros(nprop, dtype=torch.int32, device=dev)
+        voidc = torch.zeros(nprop, dtype=torch.int32, device=dev)
+        if m and nprop and prop_of.numel():
+            self._call("pg_intersections", m, int(prop_of.shape[0]), int(nprop), int(nslots), prop_of, index_map, slot, isvoid,
+                       table if nslots else None, vert, voidc)
+        return table, vert, voidc
+
+    def pg_bias_loss_forward(self, pred, coord, centroid, instance, ignore):
+        _check(pred, torch.float32, "bias_pred"); _check(coord, torch.float32, "coord"); _check(instance, torch.int64, "instance")
+        if centroid.dtype not in (torch.float32, torch.float64) or not centroid.is_contiguous():
+            raise TypeError("pg_bias_loss: instance_centroid must be a contiguous float32 or float64 tensor")
+        n, dev = int(pred.shape[0]), pred.device
+        if tuple(pred.shape) != (n, 3) or tuple(coord.shape) != (n, 3) or tuple(centroid.shape) != (n, 3) or tuple(instance.shape) != (n,):
+            raise ValueError("pg_bias_loss: bias_pred, coord, instance_centroid (n, 3) and instance (n)")
+        f64 = centroid.dtype == torch.float64
+        d = torch.empty((2, n, 3), dtype=torch.float32, device=dev)
+        acc = torch.empty(int(self.lib.pdf_pg_bias_loss_workspace_doubles()), dtype=torch.float64, device=dev)
+        loss = torch.empty(2, dtype=centroid.dtype, device=dev)
+        self._call("pg_bias_loss_forward", n, pred if n else None, coord if n else None, centroid if n else None, int(f64), instance if n else None,
+                   int(ignore), d[0] if n else None, d[1] if n else None, acc, loss)
+        return loss, d, acc
+
+    def pg_bias_loss_backward(self, d, acc, gy):
+        n = int(d.shape[1])
+        grad = torch.empty((n, 3), dtype=torch.float32, device=d.device)
+        if n:
+            self._call("pg_bias_loss_backward", n, d[0], d[1], acc, gy.contiguous(), int(gy.dtype == torch.float64), grad)
+        return grad
 
 
 _lock = threading.Lock()

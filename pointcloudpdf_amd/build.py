@@ -30,6 +30,7 @@ EXTRA = {
     "openset_metrics.hip": ["-ffp-contract=off"],   # the average-precision terms are rounded as written (quotient, quotient, product, sum)
     "grid_pool.hip": ["-ffp-contract=off"],         # the cell ids and the segment means must round like the torch expressions they replace
     "gva.hip": ["-ffp-contract=off"],               # the relation (difference, product, sum) is rounded as the torch composition rounds it
+    "point_group.hip": ["-ffp-contract=off"],       # the ball table's squared distance is the reference's expression as written
 }
 
 
@@ -59,8 +60,8 @@ def _stale(target, deps):
 
 
 # The geometry TUs again with the squared distance as an explicit FMA chain (csrc/pdfops_common.h: pdf_sqdist3): libpdfops_fma1.so /
-# libpdfops_fma2.so = the same library with those five objects swapped.  `PDFOPS_DIST_FMA=1|2` at import selects them (_native.py).
-GEOMETRY_TUS = ["knn_query.hip", "knn_grid.hip", "sampling.hip", "sampling_bucketed.hip", "ball_query.hip"]
+# libpdfops_fma2.so = the same library with those six objects swapped.  `PDFOPS_DIST_FMA=1|2` at import selects them (_native.py).
+GEOMETRY_TUS = ["knn_query.hip", "knn_grid.hip", "sampling.hip", "sampling_bucketed.hip", "ball_query.hip", "point_group.hip"]
 FMA_VARIANTS = (1, 2)
 
 

@@ -13,7 +13,7 @@
 //                  is certified by the distance to the searched cube's faces; top list in registers (static insertion)
 //   knn_scan_kernel (knn_query.hip) on the redo list
 // Work per query ~ a few hundred candidate distances instead of N_scene.  Bound: latency / VALU; HBM bytes 12N+12M+8Mk.
-#include "pdfops_common.h"
+#include "knn_grid.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -22,39 +22,6 @@ extern "C" int pdf_knn_query_list(int m, int nsample, const float *xyz, const fl
                                   const int *qcount, void *stream);
 
 namespace kg {
-
-constexpr int CAP_CELLS = 1 << 20;  // cells per scene
-// The radius queries accept d2 < r^2 OR d2 <= 1e-5: whatever the radius, a query reaches sqrt(1e-5) = 3.16228 mm.  Their 27 cells cover the
-// accepted set only if the cell is at least that wide, so the cell bound is max(radius, this) -- the same cell as before for every radius
-// from 3.1623 mm up; below it (the adaptive radius of a flat or thin scene: pad / divisor) the bound is what keeps the table exact.
-constexpr float RQ_MIN_REACH = 3.1623e-3f;
-constexpr int PB = 256;
-
-struct SceneGrid {      // 16 floats / ints per scene in the workspace
-    float minx, miny, minz, inv_h;
-    float h;
-    int nx, ny, nz;
-    int start, n;       // source point range
-    int cell_base;      // offset of this scene's cells in the cell arrays
-    int pad[5];
-};
-
-struct Layout {
-    size_t grid, cell_start, cursor, cell_of, sorted, redo, total;
-};
-__host__ __device__ inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-__host__ __device__ inline Layout make_layout(int b, int n, int m) {
-    Layout L;
-    size_t o = 0;
-    L.grid = o;       o = al(o + (size_t)b * sizeof(SceneGrid));
-    L.cell_start = o; o = al(o + ((size_t)b * CAP_CELLS + 1) * 4);
-    L.cursor = o;     o = al(o + (size_t)b * CAP_CELLS * 4);
-    L.cell_of = o;    o = al(o + (size_t)n * 4);
-    L.sorted = o;     o = al(o + (size_t)n * 16);
-    L.redo = o;       o = al(o + ((size_t)m + 4) * 4);
-    L.total = o;
-    return L;
-}
 
 // `radii` (null for every caller with a scalar cell bound): the ADAPTIVE radius of the scene, pointpdf_v1m1_base.py:137-140 --
 // min over the axes of ((hi - lo) + pad) / divisor, fp32 in that order -- is derived from the extents reduced here, written to radii[s] and
@@ -118,17 +85,6 @@ __global__ __launch_bounds__(PB) void k_grid_setup(const float *__restrict__ xyz
         g.cell_base = s * CAP_CELLS;
         grids[s] = g;
     }
-}
-
-__device__ __forceinline__ int cell_coord(float v, float lo, float inv_h, int n) {
-    int c = (int)floorf((v - lo) * inv_h);
-    return c < 0 ? 0 : (c >= n ? n - 1 : c);
-}
-
-__device__ __forceinline__ int scene_of(int i, const int *__restrict__ offset, int b) {
-    int s = 0;
-    while (s < b - 1 && i >= offset[s]) ++s;
-    return s;
 }
 
 __global__ __launch_bounds__(PB) void k_grid_hist(int n, int b, const float *__restrict__ xyz, const int *__restrict__ offset,
@@ -550,16 +506,10 @@ __global__ __launch_bounds__(256) void k_zero_words(unsigned *__restrict__ p, si
 }
 }  // namespace kg
 
-// Neighbour table of a batch with itself within a radius: idx (n, nsample) = the first nsample points of the query's scene, in index
-// order, within the radius (the query included), -1 padded; dist2 = squared distances (1e10 padded).  Same results as
-// pdf_random_ball_query with order = identity and min_radius = 0.  Workspace: pdf_knn_workspace_bytes(b, n, 0).
-// radii == null: `radius` for every scene; else the scene's adaptive radius (k_grid_setup), written to radii (b).
-static int radius_neighbors_self(int n, int nsample, float radius, float *radii, float divisor, float pad, const float *xyz, const int *offset,
-                                 int b, int *idx, float *dist2, void *workspace, long workspace_bytes, void *stream) {
-    const kg::Layout L = kg::make_layout(b, n, 0);
-    if (!workspace || workspace_bytes < (long)L.total) return PDF_ERR_BAD_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
+// The grid of the radius queries in `workspace` (make_layout(b, n, 0)): cells at least `min_cell` wide -- or, with radii, at least the scene's
+// adaptive radius (k_grid_setup), written to radii (b) -- so that the 27 cells around a point cover its ball.
+static void radius_grid_build(int n, float min_cell, float *radii, float divisor, float pad, const float *xyz, const int *offset, int b,
+                              char *ws, const kg::Layout &L, hipStream_t s) {
     kg::SceneGrid *grids = reinterpret_cast<kg::SceneGrid *>(ws + L.grid);
     unsigned *cell_start = reinterpret_cast<unsigned *>(ws + L.cell_start);
     unsigned *cursor = reinterpret_cast<unsigned *>(ws + L.cursor);
@@ -573,10 +523,34 @@ static int radius_neighbors_self(int n, int nsample, float radius, float *radii,
         kg::k_zero_words<<<pdf_divup((long)words, 1024), 256, 0, s>>>(reinterpret_cast<unsigned *>(ws + L.cell_start), words);
     }
     if (radii) kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, 1.0f, 0.f, radii, divisor, pad);   // cell >= the scene's radius
-    else kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, 1.0f, fmaxf(radius, kg::RQ_MIN_REACH) * 1.0001f, nullptr, 0.f, 0.f);   // cell >= radius
+    else kg::k_grid_setup<<<b, kg::PB, 0, s>>>(xyz, offset, grids, 1.0f, min_cell, nullptr, 0.f, 0.f);       // cell >= radius
     kg::k_grid_hist<<<pdf_divup(n, kg::PB), kg::PB, 0, s>>>(n, b, xyz, offset, grids, cell_start, cell_of);
     kg::k_grid_scan<<<b, 1024, 0, s>>>(grids, cell_start);
     kg::k_grid_scatter<<<pdf_divup(n, kg::PB), kg::PB, 0, s>>>(n, xyz, cell_of, cell_start, cursor, sorted);
+}
+
+int pdf_grid_build_min_cell(int n, const float *xyz, const int *offset, int b, float min_cell, void *workspace, long workspace_bytes,
+                            void *stream) {
+    const kg::Layout L = kg::make_layout(b, n, 0);
+    if (n < 1 || b < 1 || b > 64 || !xyz || !offset || !(min_cell > 0.f) || !workspace || workspace_bytes < (long)L.total) return PDF_ERR_BAD_ARG;
+    radius_grid_build(n, min_cell, nullptr, 0.f, 0.f, xyz, offset, b, static_cast<char *>(workspace), L, static_cast<hipStream_t>(stream));
+    return pdf_launch_status();
+}
+
+// Neighbour table of a batch with itself within a radius: idx (n, nsample) = the first nsample points of the query's scene, in index
+// order, within the radius (the query included), -1 padded; dist2 = squared distances (1e10 padded).  Same results as
+// pdf_random_ball_query with order = identity and min_radius = 0.  Workspace: pdf_knn_workspace_bytes(b, n, 0).
+// radii == null: `radius` for every scene; else the scene's adaptive radius (k_grid_setup), written to radii (b).
+static int radius_neighbors_self(int n, int nsample, float radius, float *radii, float divisor, float pad, const float *xyz, const int *offset,
+                                 int b, int *idx, float *dist2, void *workspace, long workspace_bytes, void *stream) {
+    const kg::Layout L = kg::make_layout(b, n, 0);
+    if (!workspace || workspace_bytes < (long)L.total) return PDF_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    const kg::SceneGrid *grids = reinterpret_cast<kg::SceneGrid *>(ws + L.grid);
+    const unsigned *cell_start = reinterpret_cast<unsigned *>(ws + L.cell_start);
+    const float4 *sorted = reinterpret_cast<float4 *>(ws + L.sorted);
+    radius_grid_build(n, fmaxf(radius, kg::RQ_MIN_REACH) * 1.0001f, radii, divisor, pad, xyz, offset, b, ws, L, s);
     const int grid = pdf_divup(n, kg::RQ_WAVES), block = 64 * kg::RQ_WAVES;
     if (radii) kg::k_grid_radius_self<true><<<grid, block, 0, s>>>(n, b, nsample, 0.f, radii, xyz, offset, grids, cell_start, sorted, idx, dist2);
     else kg::k_grid_radius_self<false><<<grid, block, 0, s>>>(n, b, nsample, radius, nullptr, xyz, offset, grids, cell_start, sorted, idx, dist2);

@@ -139,3 +139,57 @@ def remap_label(segment, remap_dict, remap_select=None, ignore_index=-1):
     segment_incr_remap = _lookup(segment, torch.tensor(remap, dtype=segment.dtype), segment)
     segment_incr = _lookup(segment, torch.tensor(inc, dtype=segment.dtype), torch.full_like(segment, ignore_index))
     return segment_incr_remap, segment_incr
+
+
+def instance_parser(coord, segment, instance, offset=None, segment_ignore_index=(-1, 0, 1), instance_ignore_index=-1):
+    """``InstanceParser`` (transform.py:1098-1141) on tensors of any device, for one scene (``offset=None``) or a collated batch (``offset``:
+    cumulative ends; every scene is parsed on its own, as upstream parses before it collates).
+    -> dict(instance (n) like the input: ids of the kept instances renumbered 0.. per scene in ascending id, ``instance_ignore_index``
+    on rows of an ignored class; instance_centroid (n, 3) float64: the instance's mean coordinate -- a float32 mean stored into float64,
+    as NumPy does -- or the ignore index; bbox (instances, 8) float64: centre, size, 0, class shifted down by the ignored class ids below it).
+    The inputs are not modified (upstream overwrites ``instance`` in place).  Plumbing on torch ops with one host read (the instance count);
+    min / max are exact on any device, the mean is NumPy's row-by-row float32 sum on CPU tensors (bit-equal) and a float64 prefix sum rounded
+    to float32 on the device (order-independent up to that rounding, no float atomics)."""
+    n, dev = coord.shape[0], coord.device
+    rows = torch.arange(n, device=dev)
+    scene = torch.zeros(n, dtype=torch.long, device=dev) if offset is None else torch.searchsorted(offset.to(dev).long(), rows, right=True)
+    ignored = torch.as_tensor(list(segment_ignore_index), device=dev, dtype=segment.dtype)
+    mask = ~torch.isin(segment, ignored)
+    instance = torch.where(mask, instance, torch.full_like(instance, instance_ignore_index))
+    centroid = torch.full((n, 3), float(instance_ignore_index), dtype=torch.float64, device=dev)
+    kept = instance[mask].long()
+    if kept.numel() == 0:
+        return dict(instance=instance, instance_centroid=centroid, bbox=torch.zeros((0, 8), dtype=torch.float64, device=dev))
+    lo = kept.min()
+    span = kept.max() - lo + 1
+    uniq, inverse = torch.unique(scene[mask] * span + (kept - lo), return_inverse=True)   # ascending (scene, id)
+    num = uniq.shape[0]
+    scene_of = uniq // span
+    first = torch.searchsorted(scene_of, torch.arange(int(scene.max()) + 1, device=dev))
+    instance = instance.clone()
+    instance[mask] = (inverse - first[scene_of[inverse]]).to(instance.dtype)
+    gid = torch.full((n,), -1, dtype=torch.long, device=dev)
+    gid[mask] = inverse
+    xyz = coord[mask]
+    idx3 = inverse.unsqueeze(1).expand(-1, 3)
+    bmin = torch.zeros((num, 3), dtype=coord.dtype, device=dev).scatter_reduce_(0, idx3, xyz, "amin", include_self=False)
+    bmax = torch.zeros((num, 3), dtype=coord.dtype, device=dev).scatter_reduce_(0, idx3, xyz, "amax", include_self=False)
+    count = torch.bincount(inverse, minlength=num)
+    if dev.type == "cpu":
+        import numpy as np
+
+        total = np.zeros((num, 3), xyz.numpy().dtype)
+        np.add.at(total, inverse.numpy(), xyz.numpy())          # row by row in the array's own precision: coord_.mean(0)
+        mean = torch.from_numpy(total / count.numpy()[:, None].astype(total.dtype))
+    else:
+        order = torch.argsort(inverse, stable=True)
+        run = torch.cat([torch.zeros((1, 3), dtype=torch.float64, device=dev), torch.cumsum(xyz[order].double(), 0)])
+        ends = torch.cumsum(count, 0)
+        mean = ((run[ends] - run[ends - count]) / count.unsqueeze(1)).to(coord.dtype)
+    centroid[mask] = mean[inverse].double()
+    head = torch.full((num,), n, dtype=torch.long, device=dev).scatter_reduce_(0, inverse, rows[mask], "amin", include_self=True)
+    cls = segment[head].to(coord.dtype)
+    vacancy = torch.as_tensor([float(v) for v in segment_ignore_index if v >= 0], dtype=coord.dtype, device=dev)
+    cls = cls - (cls.unsqueeze(1) > vacancy.unsqueeze(0)).sum(1).to(coord.dtype)
+    bbox = torch.cat([(bmax + bmin) / 2, bmax - bmin, torch.zeros((num, 1), dtype=coord.dtype, device=dev), cls.unsqueeze(1)], 1).double()
+    return dict(instance=instance, instance_centroid=centroid, bbox=bbox)

@@ -313,3 +313,172 @@ class IncrSegEvaluator(_Deferred):
             for key, v in m.items():
                 out[f"{key}_{name}"] = float(v)
         return out
+
+
+class InsSegEvaluator:
+    """What ``InsSegEvaluator`` logs (engines/hooks/evaluator.py:592-968): ``associate_instances`` per scene, ``evaluate_matches`` over the
+    scenes -> ``all_ap``, ``all_ap_50%``, ``all_ap_25%`` and per-class ``ap / ap50% / ap25%`` (ScanNet's instance benchmark: overlaps
+    0.5 .. 0.9 and 0.25, regions of at least 100 points).
+
+    The association never builds a mask: proposals arrive compact -- ``proposal_of`` (N): the row's proposal or -1, what ``PG-v1m1`` returns
+    next to the reference's keys; a dense ``pred_masks`` of DISJOINT masks is converted -- and every count of the reference's per-pair
+    ``logical_and`` passes (intersection with each ground-truth instance, ``vert_count``, ``void_intersection``) comes from ONE pass over the
+    points into a (proposals, instance ids) integer table (csrc/point_group.hip on device tensors, ``bincount`` on the host).  A scene record
+    is seven small arrays; the AP curves are float64 NumPy over them on the host (a few hundred numbers), pinned against the reference
+    hook's results to 1e-12 by the fixture.  ``update(...)`` per scene, ``summary()`` at the end; the records (``self.scenes``) are gathered
+    across ranks by the caller."""
+
+    def __init__(self, num_classes, names=None, segment_ignore_index=(-1,), instance_ignore_index=-1):
+        self.num_classes = int(num_classes)
+        self.names = [str(i) for i in range(self.num_classes)] if names is None else list(names)
+        self.segment_ignore_index = tuple(segment_ignore_index)
+        self.instance_ignore_index = instance_ignore_index
+        self.valid_class_names = [self.names[i] for i in range(self.num_classes) if i not in self.segment_ignore_index]
+        self.overlaps = np.append(np.arange(0.5, 0.95, 0.05), 0.25)
+        self.min_region_sizes = 100
+        self.reset()
+
+    def reset(self):
+        self.scenes, self.losses = [], []
+
+    # -- counts ---------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _proposal_of(pred):
+        if pred.get("proposal_of") is not None:
+            return pred["proposal_of"].to(torch.int32)
+        hit = pred["pred_masks"].ne(0)
+        if hit.shape[0] == 0:
+            return torch.full((hit.shape[1],), -1, dtype=torch.int32, device=hit.device)
+        if int(hit.sum(0).max()) > 1:
+            raise ValueError("InsSegEvaluator: overlapping pred_masks have no compact form; pass disjoint masks or `proposal_of`")
+        of = hit.to(torch.int8).argmax(0).to(torch.int32)
+        return torch.where(hit.any(0), of, torch.full_like(of, -1))
+
+    def intersection_table(self, proposal_of, num_proposals, segment, instance, index_map=None):
+        """-> (instance_ids (G), segment_ids (G), gt counts (G), table (P, G), vert_count (P), void_intersection (P)) as host arrays;
+        ``index_map`` (M): evaluated point j reads ``proposal_of[index_map[j]]`` (the 1-NN map to the original cloud)."""
+        dev = segment.device
+        ignored = torch.as_tensor(list(self.segment_ignore_index), device=dev, dtype=segment.dtype)
+        void = torch.isin(segment, ignored)
+        ids, inverse, counts = torch.unique(instance, return_inverse=True, return_counts=True)
+        rows = torch.arange(instance.shape[0], device=dev)
+        first = torch.full((ids.shape[0],), instance.shape[0], dtype=torch.long, device=dev).scatter_reduce_(0, inverse, rows, "amin")
+        segment_ids = segment[first]
+        g, p = int(ids.shape[0]), int(num_proposals)
+        if proposal_of.is_cuda:
+            from . import _native
+
+            table, vert, voidc = _native.hip_backend().pg_intersections(
+                proposal_of.contiguous(), p, inverse.to(torch.int32).contiguous(), g, void.contiguous(),
+                None if index_map is None else index_map.long().contiguous())
+        else:
+            of = (proposal_of if index_map is None else proposal_of[index_map.long()]).long()
+            inside = of >= 0
+            table = torch.bincount(of[inside] * g + inverse[inside], minlength=p * g).reshape(p, g)
+            vert = torch.bincount(of[inside], minlength=p)
+            voidc = torch.bincount(of[inside & void], minlength=p)
+        return tuple(t.cpu().numpy() for t in (ids, segment_ids, counts, table, vert, voidc))
+
+    def associate_instances(self, pred, segment, instance, index_map=None):
+        """The scene record the AP needs, as arrays (what the reference hook keeps as nested dicts with a mask per proposal):
+        ``gt_class / gt_size`` of the ground-truth instances that count (id not the ignore id, class not ignored; ascending id),
+        ``pr_class / pr_score / pr_size / pr_void`` of the proposals that count (class not ignored, at least ``min_region_sizes`` points;
+        in proposal order) and ``inter`` (proposals, instances): the shared point counts."""
+        classes = np.asarray(pred["pred_classes"].cpu()).astype(np.int64).reshape(-1)
+        scores = np.asarray(pred["pred_scores"].cpu()).astype(np.float64).reshape(-1)
+        of = self._proposal_of(pred).to(segment.device)
+        ids, segment_ids, counts, table, vert, voidc = self.intersection_table(of, classes.shape[0], segment, instance, index_map)
+        ignored = np.asarray(self.segment_ignore_index)
+        gt_keep = (ids != self.instance_ignore_index) & ~np.isin(segment_ids, ignored)
+        pr_keep = ~np.isin(classes, ignored) & (vert >= self.min_region_sizes)
+        return dict(gt_class=segment_ids[gt_keep].astype(np.int64), gt_size=counts[gt_keep].astype(np.int64),
+                    pr_class=classes[pr_keep], pr_score=scores[pr_keep], pr_size=vert[pr_keep].astype(np.int64),
+                    pr_void=voidc[pr_keep].astype(np.int64), inter=table[pr_keep][:, gt_keep].astype(np.int64))
+
+    @torch.no_grad()
+    def update(self, output_dict, input_dict):
+        """One validation scene: the model's eval output and its input (``segment``, ``instance``; with ``origin_coord`` the proposals are
+        carried to the original cloud through ``pointops.knn_query(1, ...)`` and scored against ``origin_segment`` / ``origin_instance``)."""
+        segment, instance, index_map = input_dict["segment"], input_dict["instance"], None
+        if "origin_coord" in input_dict:
+            from . import pointops
+
+            idx, _ = pointops.knn_query(1, input_dict["coord"].float(), input_dict["offset"].int(), input_dict["origin_coord"].float(),
+                                        input_dict["origin_offset"].int())
+            index_map = idx.flatten().long()
+            segment, instance = input_dict["origin_segment"], input_dict["origin_instance"]
+        self.scenes.append(self.associate_instances(output_dict, segment, instance, index_map))
+        if output_dict.get("loss") is not None:
+            self.losses.append(float(output_dict["loss"]))
+
+    # -- average precision (float64 on the host) ---------------------------------------------------------------------------------------
+    def _scene_records(self, scene, cls, threshold):
+        """One scene, one class, one overlap threshold -> (scores of the true positives, scores of the false positives, missed instances,
+        has an instance that counts, has a proposal).  Rules of the ScanNet benchmark as the reference hook applies them: instances in
+        order, each takes the first free proposal whose IoU exceeds the threshold and keeps the best score among all free ones that do
+        (the others are false positives); a proposal that exceeds the threshold with no instance of its class is a false positive unless
+        more than ``threshold`` of it lies on ignored ground (void points and instances below ``min_region_sizes``)."""
+        g, p = scene["gt_class"] == cls, scene["pr_class"] == cls
+        inter = scene["inter"][p][:, g]
+        gsize, psize, score = scene["gt_size"][g], scene["pr_size"][p], scene["pr_score"][p]
+        iou = inter / np.maximum(gsize[None, :] + psize[:, None] - inter, 1)
+        over = (inter > 0) & (iou > threshold)
+        big = gsize >= self.min_region_sizes
+        taken = np.zeros(psize.shape[0], bool)
+        hits, false_alarms, missed = [], [], 0
+        for j in np.nonzero(big)[0]:
+            free = np.nonzero(over[:, j] & ~taken)[0]
+            if free.size == 0:
+                missed += 1
+                continue
+            taken[free[0]] = True
+            ranked = np.sort(score[free])
+            hits.append(ranked[-1])
+            false_alarms.extend(ranked[:-1])
+        lonely = ~over.any(1)
+        on_ignored = scene["pr_void"][p] + inter[:, ~big].sum(1)
+        false_alarms.extend(score[lonely & (on_ignored / np.maximum(psize, 1) <= threshold)])
+        return hits, false_alarms, missed, bool(big.any()), bool(p.any())
+
+    @staticmethod
+    def _average_precision(hits, false_alarms, missed):
+        """Area under the precision-recall curve with one operating point per distinct score and the benchmark's half-step widths."""
+        score = np.concatenate([np.asarray(hits, float), np.asarray(false_alarms, float)])
+        truth = np.concatenate([np.ones(len(hits)), np.zeros(len(false_alarms))])
+        order = np.argsort(score, kind="stable")
+        score, truth = score[order], truth[order]
+        _, first = np.unique(score, return_index=True)              # operating point k keeps the records from first[k] on
+        below = np.concatenate([[0.0], np.cumsum(truth)])[first]    # true records under the point
+        tp = truth.sum() - below
+        kept = score.shape[0] - first
+        precision = np.append(tp / np.maximum(kept, 1), 1.0)
+        recall = np.append(tp / np.maximum(tp + below + missed, 1), 0.0)
+        padded = np.concatenate([recall[:1], recall, [0.0]])
+        return float(np.dot(precision, 0.5 * (padded[:-2] - padded[2:])))
+
+    def evaluate_matches(self, scenes):
+        """Scene records -> the hook's dict: ``all_ap`` (mean over classes and the overlaps 0.5 .. 0.9), ``all_ap_50%``, ``all_ap_25%``,
+        ``classes[name]`` = ``ap / ap50% / ap25%``.  A class without instances is NaN (left out of the means), one with instances but no
+        proposal 0."""
+        class_ids = [i for i in range(self.num_classes) if i not in self.segment_ignore_index]
+        table = np.full((len(class_ids), len(self.overlaps)), np.nan)
+        for ci, cls in enumerate(class_ids):
+            for ti, threshold in enumerate(self.overlaps):
+                parts = [self._scene_records(scene, cls, threshold) for scene in scenes]
+                has_gt, has_pred = any(r[3] for r in parts), any(r[4] for r in parts)
+                if has_gt and has_pred:
+                    table[ci, ti] = self._average_precision([v for r in parts for v in r[0]], [v for r in parts for v in r[1]],
+                                                            sum(r[2] for r in parts))
+                elif has_gt:
+                    table[ci, ti] = 0.0
+        is25, is50 = np.isclose(self.overlaps, 0.25), np.isclose(self.overlaps, 0.5)
+        out = {"all_ap": np.nanmean(table[:, ~is25]), "all_ap_50%": np.nanmean(table[:, is50]), "all_ap_25%": np.nanmean(table[:, is25]),
+               "classes": {}}
+        for ci, name in enumerate(self.valid_class_names):
+            out["classes"][name] = {"ap": np.mean(table[ci, ~is25]), "ap50%": np.mean(table[ci, is50]), "ap25%": np.mean(table[ci, is25])}
+        return out
+
+    def summary(self):
+        out = self.evaluate_matches(self.scenes)
+        out["loss"] = float(np.mean(self.losses)) if self.losses else float("nan")
+        return out

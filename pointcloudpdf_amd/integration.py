@@ -4,24 +4,26 @@ import sys
 
 def install_pointops():
     """Make ``import pointops`` (libs/pointops/functions/__init__.py:1-14 names) and ``import pointops2.pointops``
-    (the window-attention part, libs/pointops2/functions/pointops.py) resolve to this package's drop-ins."""
-    from . import pointops, pointops2
+    (the window-attention part, libs/pointops2/functions/pointops.py) and ``import pointgroup_ops`` (libs/pointgroup_ops:
+    ``ballquery_batch_p``, ``bfs_cluster``) resolve to this package's drop-ins."""
+    from . import pointgroup_ops, pointops, pointops2
 
     sys.modules["pointops"] = pointops
     # libs/pointops2: ``import pointops2.pointops as pointops`` (stratified_transformer_v1m1_origin.py:21)
     sys.modules["pointops2"] = pointops2
     sys.modules["pointops2.pointops"] = pointops2.pointops
+    sys.modules["pointgroup_ops"] = pointgroup_ops
     return pointops
 
 
 def register_into_pointcept(force=True):
     """Register our classes under the reference's names in a live pointcept install's registries."""
     from pointcept.models.builder import MODELS as PC_MODELS  # noqa: import error = pointcept not importable
-    from . import cac, point_transformer, point_transformer_v2, point_transformer_v3, recognizer, segmentor, model_hook, sparse_unet, stratified  # noqa: F401  (fills the registries)
+    from . import cac, point_group, point_transformer, point_transformer_v2, point_transformer_v3, recognizer, segmentor, model_hook, sparse_unet, stratified  # noqa: F401  (fills the registries)
     from .registry import MODELS, RECOGNIZER, MODELHOOKS
 
     for name in ["PointTransformer-Seg26", "PointTransformer-Seg38", "PointTransformer-Seg50",
-                 "PointTransformer-Recognizer", "ST-v1m1", "ST-v1m1-Recognizer", "PT-v2m2", "DefaultSegmentor", "CAC-v1m1", "SpUNet-v1m1", "PT-v3m1", "DefaultSegmentorV2"]:
+                 "PointTransformer-Recognizer", "ST-v1m1", "ST-v1m1-Recognizer", "PT-v2m2", "DefaultSegmentor", "CAC-v1m1", "SpUNet-v1m1", "PT-v3m1", "DefaultSegmentorV2", "PG-v1m1"]:
         PC_MODELS.register_module(name=name, force=force, module=MODELS.get(name))
     try:
         from pointcept.recognizers.builder import RECOGNIZER as PC_REC
