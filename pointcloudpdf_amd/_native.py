@@ -26,7 +26,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 18   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 19   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_long = ctypes.c_long
@@ -804,6 +804,18 @@ class HipBackend(CBackend):
         lib.pdf_linbn_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
         lib.pdf_linbn_backward.restype = c_int
         lib.pdf_linbn_backward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]
+        lib.pdf_transition_up_supported.restype = c_int
+        lib.pdf_transition_up_supported.argtypes = [c_int, c_int, c_int]
+        lib.pdf_transition_up_forward.restype = c_int
+        lib.pdf_transition_up_forward.argtypes = [c_long, c_int, c_long, c_int, c_int, c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
+        lib.pdf_transition_up_backward.restype = c_int
+        lib.pdf_transition_up_backward.argtypes = [c_long, c_int, c_long, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
+        lib.pdf_bn_coef_from_partial2.restype = c_int
+        lib.pdf_bn_coef_from_partial2.argtypes = [c_int, c_long, c_int, c_int, c_long, c_int, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p]
+        lib.pdf_bn_act_backward2.restype = c_int
+        lib.pdf_bn_act_backward2.argtypes = [c_long, c_int, c_long, c_int, c_void_p, c_int, c_void_p]
+        lib.pdf_rowlin_wgrad2.restype = c_int
+        lib.pdf_rowlin_wgrad2.argtypes = [c_long, c_int, c_int, c_long, c_int, c_int, c_void_p, c_int, c_void_p]
         lib.pdf_bottleneck_forward.restype = c_int
         lib.pdf_bottleneck_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_int, c_int, c_void_p]
         lib.pdf_bottleneck_backward.restype = c_int

@@ -9,6 +9,7 @@
 // from C instead of from ~30 Python-level tensor ops removes most of that host time.  Everything here is launch sequencing;
 // the kernels live in rowlin.hip / pointwise.hip.  Scratch and saved activations are caller-owned (no allocation).
 #include "pdfops_common.h"
+#include <initializer_list>
 
 namespace {
 struct Err {
@@ -292,5 +293,92 @@ extern "C" int pdf_linbn_backward(long n, int k, int o, void *const *p, int trai
                              grads + ok + o, gz, nullptr, stream);                                                    // [dbeta | dgamma]
     if (p[5]) e << pdf_rowlin_forward(n, o, k, gz, o, (const float *)p[4], 1, nullptr, nullptr, nullptr, 0, (float *)p[5], k, 0, nullptr, mma_input, stream);
     e << pdf_rowlin_wgrad(n, k, o, gz, o, (const float *)p[1], k, nullptr, nullptr, 0, grads, grads + ok, (float *)p[9], mma_input, stream);    // dW, db
+    return e.rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// TransitionUp with two inputs (point_transformer_seg.py:162-167): out = relu(bn1(x1 W1^T + b1)) + interpolation(relu(bn2(x2 W2^T + b2)))
+// as ONE host call per direction.  The two Linear -> BatchNorm chains are independent of each other until the join, so their small
+// kernels run as two-problem launches (pdfops_common.h), and the norm applies, the interpolation and the add are one pass over z1 / z2
+// (gather_ops.hip: k_tu_join): 4 launches forward and 9 backward against 8 and 13 of two pdf_linbn_* nodes + interpolation + add.  Every
+// product, partial row and sum is formed by the same kernel body over the same grid as there: the results are the same bits.
+// Train mode only (batch statistics); both norms share eps and momentum.
+extern "C" int pdf_transition_up_supported(int k1, int k2, int o) {
+    return pdf_rowlin_streams(k1, o) && pdf_rowlin_streams(k2, o) && k1 % 32 == 0 && k2 % 32 == 0 && o % 32 == 0 && pdf_bn_supported(o);
+}
+static bool tu_aligned(void *const *p, std::initializer_list<int> which) {   // the tensors read or written 16 bytes at a time
+    uintptr_t all = 0;
+    for (int i : which) all |= reinterpret_cast<uintptr_t>(p[i]);
+    return (all & 15) == 0;
+}
+static bool tu_sizes_ok(long n1, long n2, int o) {   // 32-bit element counts of the gather kernels
+    return n1 * (o / 4) < (1L << 31) && n2 * (o / 4) < (1L << 31) && n1 * 3 < (1L << 31);
+}
+
+// Forward p[]: 0 x1 (n1,k1) 1 W1 (o,k1) 2 b1 or null 3 gamma1 4 beta1 5 rm1 6 rv1 | 7 x2 (n2,k2) 8 W2 (o,k2) 9 b2 or null 10 gamma2 11 beta2 12 rm2 13 rv2
+//              14 idx (n1,3) int32, rows of x2 or -1  15 weight (n1,3)  16 visiting order of the n1 rows or null
+//              17 z1 (n1,o) 18 coef1 (4o) 19 partial1 (pdf_rowlin_partial_floats(n1,o)) | 20 z2 (n2,o) 21 coef2 (4o) 22 partial2 (.. n2) | 23 out (n1,o)
+extern "C" int pdf_transition_up_forward(long n1, int k1, long n2, int k2, int o, void *const *p, int training, float eps, float momentum,
+                                         int mma_input, void *stream) {
+    if (n1 < 1 || n2 < 1 || !p || mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    for (int i = 0; i < 24; ++i)
+        if (!p[i] && i != 2 && i != 9 && i != 16) return PDF_ERR_BAD_ARG;
+    if (!training || !pdf_transition_up_supported(k1, k2, o) || !tu_sizes_ok(n1, n2, o) || !tu_aligned(p, {0, 1, 7, 8, 17, 18, 20, 21, 23})) return PDF_ERR_UNSUPPORTED;
+    Err e;
+    PdfBnFinalize2 f;
+    const long n[2] = {n1, n2};
+    const int k[2] = {k1, k2};
+    for (int i = 0; i < 2; ++i) {
+        void *const *t = p + 7 * i;
+        float *z = (float *)p[17 + 3 * i], *partial = (float *)p[19 + 3 * i];
+        e << pdf_rowlin_forward(n[i], k[i], o, (const float *)t[0], k[i], (const float *)t[1], 0, (const float *)t[2], nullptr, nullptr, 0, z, o, 0, partial,
+                                mma_input, stream);
+        f.partial[i] = partial; f.rows[i] = pdf_rowlin_partial_rows(n[i], k[i], o); f.nch[i] = o; f.count[i] = (double)n[i];
+        f.gamma[i] = (const float *)t[3]; f.beta[i] = (const float *)t[4]; f.running_mean[i] = (float *)t[5]; f.running_var[i] = (float *)t[6];
+        f.coef[i] = (float *)p[18 + 3 * i];
+    }
+    f.split = 0;
+    if (e.rc) return e.rc;
+    e << pdf_bn_finalize2(f, eps, momentum, stream);
+    e << pdf_tu_join(n1, o, (const float *)p[17], (const float *)p[18], (const float *)p[20], (const float *)p[21], (const int *)p[14],
+                     (const float *)p[15], (const int *)p[16], (float *)p[23], stream);
+    return e.rc;
+}
+
+// Backward p[]: 0 g (n1,o) | 1 x1 2 z1 3 coef1 4 W1 | 5 x2 6 z2 7 coef2 8 W2 | 9 weight (n1,3) 10 inv_off (n2+1) 11 inv_entry 12 source order of the n2 rows or null
+//               13 gx1 (n1,k1) or null 14 gx2 (n2,k2) or null (a null input gradient is not computed)
+//               15 grads1 [dW1 (o*k1) | db1 (o) | dbeta1 (o) | dgamma1 (o)] 16 grads2 (.. k2)   (every element is WRITTEN: no zeroing)
+//               17 g2 (n2,o) 18 gz1 (n1,o) 19 gz2 (n2,o) 20 partial1 (pdf_bn_partial_floats(n1,o)) 21 partial2 (.. n2)
+//               22 ws1 (pdf_rowlin_wgrad_ws_floats(n1,k1,o,1)) 23 ws2 (.. n2,k2)   (scratch)
+extern "C" int pdf_transition_up_backward(long n1, int k1, long n2, int k2, int o, void *const *p, int entry_base, int mma_input, void *stream) {
+    if (n1 < 1 || n2 < 1 || !p || mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    for (int i = 0; i < 24; ++i)
+        if (!p[i] && i != 12 && i != 13 && i != 14) return PDF_ERR_BAD_ARG;
+    if (!pdf_transition_up_supported(k1, k2, o) || !tu_sizes_ok(n1, n2, o) || !tu_aligned(p, {0, 1, 2, 3, 5, 6, 7, 15, 16, 17, 18, 19})) return PDF_ERR_UNSUPPORTED;
+    const float *g = (const float *)p[0];
+    float *g2 = (float *)p[17];
+    const long n[2] = {n1, n2};
+    const int k[2] = {k1, k2};
+    Err e;
+    e << pdf_seg_sum_weighted_ordered(n2, o, 3, 1, g, (const float *)p[9], (const int *)p[10], (const int *)p[11], entry_base, (const int *)p[12], g2, stream);
+    if (e.rc) return e.rc;
+    PdfBnBwd2 b;
+    PdfWgrad2 w;
+    for (int i = 0; i < 2; ++i) {
+        void *const *t = p + 1 + 4 * i;   // x z coef W
+        float *grads = (float *)p[15 + i];
+        const long ok = (long)o * k[i];
+        b.n[i] = n[i]; b.c[i] = o; b.gy[i] = i ? g2 : g; b.x[i] = (const float *)t[1]; b.coef[i] = (const float *)t[2];
+        b.partial[i] = (float *)p[20 + i]; b.sums[i] = grads + ok + o; b.gx[i] = (float *)p[18 + i];
+        w.n[i] = n[i]; w.k[i] = k[i]; w.o[i] = o; w.g[i] = b.gx[i]; w.x[i] = (const float *)t[0]; w.dw[i] = grads; w.db[i] = grads + ok;
+        w.ws[i] = (float *)p[22 + i];
+    }
+    b.split = 0;
+    e << pdf_bn_backward2(b, 1, stream);
+    for (int i = 0; i < 2; ++i)
+        if (p[13 + i])
+            e << pdf_rowlin_forward(n[i], o, k[i], b.gx[i], o, (const float *)p[4 + 4 * i], 1, nullptr, nullptr, nullptr, 0, (float *)p[13 + i], k[i], 0, nullptr,
+                                    mma_input, stream);
+    e << pdf_rowlin_wgrad_pair(w, mma_input, stream);
     return e.rc;
 }

@@ -908,6 +908,21 @@ struct BnpClosed {
     int col_g;                    // first column of G in the partial rows
     float *out4;
 };
+// one block of 16 columns (body of k_colsum and of its two-problem form)
+__device__ __forceinline__ void colsum_block(const float *__restrict__ partial, int rows, int width, int stride, float *__restrict__ out,
+                                             unsigned block, double (*red)[17]) {
+    const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int col = block * 16 + cl;
+    const double v = wave_rows_sum(col < width ? strided_sum(partial + col, (size_t)stride, rl, rows) : 0.0);
+    if ((threadIdx.x & 63) < 16) red[threadIdx.x >> 6][cl] = v;
+    __syncthreads();
+    if (rl != 0 || col >= width) return;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < RED_WAVES; ++k) s += red[k][cl];
+    out[col] = (float)s;
+}
+
 __global__ __launch_bounds__(RED_THREADS) void k_colsum(const float *__restrict__ partial, int rows, int width, int stride, float *__restrict__ out,
                                                         BnpClosed bc) {
     __shared__ double red[RED_WAVES][17];
@@ -947,29 +962,19 @@ __global__ __launch_bounds__(RED_THREADS) void k_colsum(const float *__restrict_
         }
         return;
     }
-    const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const int col = blockIdx.x * 16 + cl;
-    const double v = wave_rows_sum(col < width ? strided_sum(partial + col, (size_t)stride, rl, rows) : 0.0);
-    if ((threadIdx.x & 63) < 16) red[threadIdx.x >> 6][cl] = v;
-    __syncthreads();
-    if (rl != 0 || col >= width) return;
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < RED_WAVES; ++k) s += red[k][cl];
-    out[col] = (float)s;
+    colsum_block(partial, rows, width, stride, out, blockIdx.x, red);
 }
 
 // ------------------------------------------------------------------------------------------------ BN finalize
 // partial: [rows][2*nch] (sum | sumsq).  Train: batch mean/var -> scale/shift (+ running-stat update, saved mean/rstd).
 // block = 16 channels x RED_RL row-lanes: every row-lane sums a strided subset of the partial rows in double, LDS combine.
-__global__ __launch_bounds__(RED_THREADS) void k_bn_finalize(const float *__restrict__ partial, int rows, int nch, double count,
+__device__ __forceinline__ void bn_finalize_block(const float *__restrict__ partial, int rows, int nch, double count,
                               const float *__restrict__ gamma, const float *__restrict__ beta, float eps, float momentum,
                               float *__restrict__ running_mean, float *__restrict__ running_var,
                               float *__restrict__ scale, float *__restrict__ shift, float *__restrict__ mean_out,
-                              float *__restrict__ rstd_out) {
-    __shared__ double red[2][RED_WAVES][17];
+                              float *__restrict__ rstd_out, unsigned block, double (*red)[RED_WAVES][17]) {
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const int ch = blockIdx.x * 16 + cl;
+    const int ch = block * 16 + cl;
     const double a = wave_rows_sum(ch < nch ? strided_sum(partial + ch, 2 * (size_t)nch, rl, rows) : 0.0);
     const double b = wave_rows_sum(ch < nch ? strided_sum(partial + nch + ch, 2 * (size_t)nch, rl, rows) : 0.0);
     if ((threadIdx.x & 63) < 16) { red[0][threadIdx.x >> 6][cl] = a; red[1][threadIdx.x >> 6][cl] = b; }
@@ -992,6 +997,30 @@ __global__ __launch_bounds__(RED_THREADS) void k_bn_finalize(const float *__rest
         running_mean[ch] = (1.f - momentum) * running_mean[ch] + momentum * (float)mean;
         running_var[ch] = (1.f - momentum) * running_var[ch] + momentum * (float)unbiased;
     }
+}
+__global__ __launch_bounds__(RED_THREADS) void k_bn_finalize(const float *__restrict__ partial, int rows, int nch, double count,
+                              const float *__restrict__ gamma, const float *__restrict__ beta, float eps, float momentum,
+                              float *__restrict__ running_mean, float *__restrict__ running_var,
+                              float *__restrict__ scale, float *__restrict__ shift, float *__restrict__ mean_out,
+                              float *__restrict__ rstd_out) {
+    __shared__ double red[2][RED_WAVES][17];
+    bn_finalize_block(partial, rows, nch, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, mean_out, rstd_out,
+                      blockIdx.x, red);
+}
+
+// Two independent problems in ONE launch (the two norms of a TransitionUp join): workgroups below `split` work on problem 0 with their own
+// id, the rest on problem 1 with id - split.  Each problem keeps the grid of its single launch (16 channels / columns per workgroup), so
+// every sum is formed exactly as there.
+__global__ __launch_bounds__(RED_THREADS) void k_bn_finalize2(PdfBnFinalize2 q, float eps, float momentum) {
+    __shared__ double red[2][RED_WAVES][17];
+    const int i = blockIdx.x >= (unsigned)q.split ? 1 : 0;
+    bn_finalize_block(q.partial[i], q.rows[i], q.nch[i], q.count[i], q.gamma[i], q.beta[i], eps, momentum, q.running_mean[i], q.running_var[i],
+                      q.coef[i], q.coef[i] + q.nch[i], q.coef[i] + 2 * q.nch[i], q.coef[i] + 3 * q.nch[i], blockIdx.x - (i ? q.split : 0), red);
+}
+__global__ __launch_bounds__(RED_THREADS) void k_colsum2(PdfColsum2 q) {
+    __shared__ double red[RED_WAVES][17];
+    const int i = blockIdx.x >= (unsigned)q.split ? 1 : 0;
+    colsum_block(q.partial[i], q.rows[i], q.width[i], q.width[i], q.out[i], blockIdx.x - (i ? q.split : 0), red);
 }
 
 // Eval: scale/shift from running statistics.
@@ -1024,6 +1053,15 @@ void launch_colsum(const float *partial, int rows, int width, float *out, hipStr
     none.mom = nullptr; none.out4 = nullptr; none.rows = 0.0; none.col_g = 0;
     none.Wp1 = none.bp1 = none.sp = none.mean = none.rstd = as_const(nullptr);
     k_colsum<<<pdf_divup(width, 16), RED_THREADS, 0, s>>>(partial, rows, width, width, out, none);
+}
+
+void launch_bn_finalize2(PdfBnFinalize2 q, float eps, float momentum, hipStream_t s) {
+    q.split = pdf_divup(q.nch[0], 16);
+    k_bn_finalize2<<<q.split + pdf_divup(q.nch[1], 16), RED_THREADS, 0, s>>>(q, eps, momentum);
+}
+void launch_colsum2(PdfColsum2 q, hipStream_t s) {
+    q.split = pdf_divup(q.width[0], 16);
+    k_colsum2<<<q.split + pdf_divup(q.width[1], 16), RED_THREADS, 0, s>>>(q);
 }
 
 template <typename KernelT>

@@ -409,6 +409,46 @@ __global__ __launch_bounds__(GB) void interp_fwd_ord(unsigned total, FastDiv cvd
     st_stream(output + (unsigned long)r * cv + col, acc);
 }
 
+// The join of a TransitionUp (point_transformer_seg.py:164-167) in one pass over the pre-norm rows z1 (fine level) and z2 (coarse level):
+//     out[r] = relu(z1[r] s1 + t1) + sum_{i ascending} (idx[r, i] >= 0 ? relu(z2[idx[r, i]] s2 + t2) : 0) w[r, i]
+// -- what pw::k_bn_apply<false> (twice), interp_fwd_ord<3> and the element-wise add compute through three activation-sized tensors.  The
+// arithmetic is theirs, operation for operation, with the contractions spelled out: fma(z, s, t) + 0 then max; acc = fma(v, w, acc) from
+// acc = 0; y1 + acc.  Same lane mapping, visiting order and streamed store as interp_fwd_ord.
+__device__ __forceinline__ v4f tu_norm_relu(v4f z, v4f s, v4f t) {
+    v4f o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = fmaxf(__fadd_rn(__fmaf_rn(z[e], s[e], t[e]), 0.f), 0.f);
+    return o;
+}
+template <int K>
+__global__ __launch_bounds__(GB) void k_tu_join(unsigned total, FastDiv cvd, const int *__restrict__ order, const v4f *__restrict__ z1,
+                                                const v4f *__restrict__ coef1, const v4f *__restrict__ z2, const v4f *__restrict__ coef2,
+                                                const int *__restrict__ idx, const float *__restrict__ weight, v4f *__restrict__ output) {
+    const unsigned cv = cvd.d, blk = xcd_chunked_block(blockIdx.x, gridDim.x);
+    const unsigned w = blk * GB + threadIdx.x;
+    if (w >= total) return;
+    const unsigned sq = fdiv(w, cvd), col = w - sq * cv, r = order ? (unsigned)order[sq] : sq;
+    int j[K]; float wt[K]; v4f v[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) { j[i] = idx[(unsigned long)r * K + i]; wt[i] = weight[(unsigned long)r * K + i]; }
+#pragma unroll
+    for (int i = 0; i < K; ++i) v[i] = z2[(unsigned long)max(j[i], 0) * cv + col];
+    const v4f own = z1[(unsigned long)r * cv + col];
+    const v4f s1 = coef1[col], t1 = coef1[cv + col], s2 = coef2[col], t2 = coef2[cv + col];   // coef = scale | shift | mean | rstd
+    v4f acc = (v4f)(0.f);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const v4f a = j[i] >= 0 ? tu_norm_relu(v[i], s2, t2) : (v4f)(0.f);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = __fmaf_rn(a[e], wt[i], acc[e]);
+    }
+    const v4f y1 = tu_norm_relu(own, s1, t1);
+    v4f o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = __fadd_rn(y1[e], acc[e]);
+    st_stream(output + (unsigned long)r * cv + col, o);
+}
+
 __global__ __launch_bounds__(GB) void agg_fwd_ord(unsigned total, FastDiv cvd, int nsample, unsigned wv, const int *__restrict__ order,
                                                   const v4f *__restrict__ input, const v4f *__restrict__ position,
                                                   const v4f *__restrict__ weight, const int *__restrict__ idx, v4f *__restrict__ output) {
@@ -860,6 +900,18 @@ extern "C" int pdf_interpolation_forward_ordered(int n, int c, int k, const floa
         return pdf_launch_status();
     }
     DISPATCH_VEC(v, (interp_fwd_kernel<V><<<grid_for((long)n * (c / V)), GB, 0, s>>>(n, c / V, k, input, idx, weight, output)));
+    return pdf_launch_status();
+}
+
+// out (n1, o) = relu(bn1(z1)) + interpolation(relu(bn2(z2))) for three neighbours per row (k_tu_join); coef_i = scale | shift | ... of norm i.
+// idx (n1, 3) holds rows of z2 or -1; order: visiting order of the n1 rows or null.  (csrc/block.hip: pdf_transition_up_forward)
+int pdf_tu_join(long n1, int o, const float *z1, const float *coef1, const float *z2, const float *coef2, const int *idx, const float *weight,
+                const int *order, float *out, void *stream) {
+    if (n1 < 1 || !z1 || !coef1 || !z2 || !coef2 || !idx || !weight || !out) return PDF_ERR_BAD_ARG;
+    if (o < 4 || (o & 3) || n1 * (o / 4) >= (1L << 31) || n1 * 3 >= (1L << 31)) return PDF_ERR_UNSUPPORTED;
+    const unsigned total = (unsigned)(n1 * (o / 4));
+    k_tu_join<3><<<(total + GB - 1) / GB, GB, 0, static_cast<hipStream_t>(stream)>>>(total, mk_fastdiv(o / 4), order, (const v4f *)z1, (const v4f *)coef1,
+                                                                                    (const v4f *)z2, (const v4f *)coef2, idx, weight, (v4f *)out);
     return pdf_launch_status();
 }
 

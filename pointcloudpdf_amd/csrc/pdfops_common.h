@@ -155,6 +155,46 @@ int pdf_bn_apply_rows(long n, int c, const float *x, const float *res, const flo
                       float *running_mean, float *running_var, float eps, float momentum, float *coef, void *handoff, int relu, float *y,
                       void *stream);             // pointwise.hip
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Two-problem forms of the small kernels (the two Linear -> BatchNorm chains of a TransitionUp join are independent of each other): ONE
+// launch whose workgroups below `split` run problem 0 with their own id and the rest problem 1 with id - split.  Each problem keeps the
+// grid its single launch has, so partial rows and sums are formed exactly as there.  `split` is filled in by the launcher.
+struct PdfBnFinalize2 {          // fl::k_bn_finalize twice; coef (4 nch) = scale | shift | mean | rstd
+    const float *partial[2]; int rows[2], nch[2]; double count[2];
+    const float *gamma[2], *beta[2]; float *running_mean[2], *running_var[2], *coef[2];
+    int split;
+};
+struct PdfColsum2 {              // fl::k_colsum twice: out (width) = column sums of partial [rows][width]
+    const float *partial[2]; int rows[2], width[2]; float *out[2];
+    int split;
+};
+struct PdfBnBwd2 {               // pw::k_bn_bwd_reduce<false> / pw::k_bn_bwd_apply<false> twice (relu given per launch)
+    long n[2]; int c[2];
+    const float *gy[2], *x[2], *coef[2];
+    float *partial[2];           // reduce: [grid_rows(n, c)][2 c]
+    float *sums[2];              // [d beta | d gamma] (2 c): written by the column sums, read by the apply
+    float *gx[2];
+    int split;
+};
+namespace fl {  // fused_layer.hip
+void launch_bn_finalize2(PdfBnFinalize2 q, float eps, float momentum, hipStream_t s);
+void launch_colsum2(PdfColsum2 q, hipStream_t s);
+}
+int pdf_bn_finalize2(PdfBnFinalize2 q, float eps, float momentum, void *stream);   // pointwise.hip
+int pdf_bn_backward2(PdfBnBwd2 q, int relu, void *stream);                         // pointwise.hip: reduce -> column sums -> apply, 3 launches
+// rowlin.hip: the two weight-gradient products (rl2::k_wg, one launch each, own workspace) followed by ONE two-problem slab reduction.
+// Streaming shapes only (PDF_ERR_UNSUPPORTED otherwise).  ws[i]: pdf_rowlin_wgrad_ws_floats(n[i], k[i], o[i], 1) floats; db[i] may be null.
+struct PdfWgrad2 {
+    long n[2]; int k[2], o[2];
+    const float *g[2], *x[2];
+    float *dw[2], *db[2], *ws[2];
+};
+int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream);
+int pdf_rowlin_streams(int k, int o);   // rowlin.hip: (k, o) is a shape of the streaming kernels (rl2)
+// gather_ops.hip: out (n1, o) = relu(bn1(z1)) + interpolation(relu(bn2(z2))) over (n1, 3) tables, one pass
+int pdf_tu_join(long n1, int o, const float *z1, const float *coef1, const float *z2, const float *coef2, const int *idx, const float *weight,
+                const int *order, float *out, void *stream);
+
 // producer side: any ONE workgroup of the kernel that writes the rows (before or after its own work; the kernel boundary orders it)
 __device__ __forceinline__ void pdf_handoff_zero(unsigned long long *gran, int c, unsigned *sync) {
     for (int e = threadIdx.x; e < 2 * c; e += blockDim.x) gran[e] = 0ull;

@@ -93,12 +93,13 @@ __global__ __launch_bounds__(PB) void k_bn_apply_rows(long n4, int c4, const flo
 }
 
 // partial[block][2c] = sum g' | sum g' * xhat,   g' = gy masked by the ReLU (recomputed from x, res)
+// (block / nblocks: the workgroup's id and the grid of ITS problem -- blockIdx.x / gridDim.x in the single-problem kernel)
 template <bool RES>
-__global__ __launch_bounds__(PB) void k_bn_bwd_reduce(long n, int c, const float *__restrict__ gy, const float *__restrict__ x,
-                                                      const float *__restrict__ res, const float *__restrict__ scale,
-                                                      const float *__restrict__ shift, const float *__restrict__ mean,
-                                                      const float *__restrict__ rstd, int relu, float *partial) {
-    extern __shared__ float red[];
+__device__ __forceinline__ void bn_bwd_reduce_block(long n, int c, const float *__restrict__ gy, const float *__restrict__ x,
+                                                    const float *__restrict__ res, const float *__restrict__ scale,
+                                                    const float *__restrict__ shift, const float *__restrict__ mean,
+                                                    const float *__restrict__ rstd, int relu, float *partial, unsigned block, unsigned nblocks,
+                                                    float *red) {
     const int tpr = c / 4, rpb = PB / tpr;
     const int tr = threadIdx.x / tpr, tc = threadIdx.x % tpr;
     float s[4] = {0.f, 0.f, 0.f, 0.f}, sx[4] = {0.f, 0.f, 0.f, 0.f};
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(PB) void k_bn_bwd_reduce(long n, int c, const float
         float sc[4], sh[4], mu[4], rs[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { sc[k] = scale[tc * 4 + k]; sh[k] = shift[tc * 4 + k]; mu[k] = mean[tc * 4 + k]; rs[k] = rstd[tc * 4 + k]; }
-        for (long r = (long)blockIdx.x * rpb + tr; r < n; r += (long)gridDim.x * rpb) {
+        for (long r = (long)block * rpb + tr; r < n; r += (long)nblocks * rpb) {
             const float4 g4 = *reinterpret_cast<const float4 *>(gy + r * c + tc * 4);
             const float4 x4 = *reinterpret_cast<const float4 *>(x + r * c + tc * 4);
             const float4 r4 = RES ? *reinterpret_cast<const float4 *>(res + r * c + tc * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -129,19 +130,36 @@ __global__ __launch_bounds__(PB) void k_bn_bwd_reduce(long n, int c, const float
             float a = 0.f;
             for (int rr = 0; rr < rpb; ++rr) a += red[(rr * tpr + threadIdx.x) * 8 + k];
             const int ch = threadIdx.x * 4 + (k & 3);
-            partial[(size_t)blockIdx.x * 2 * c + (k < 4 ? ch : c + ch)] = a;
+            partial[(size_t)block * 2 * c + (k < 4 ? ch : c + ch)] = a;
         }
     }
+}
+template <bool RES>
+__global__ __launch_bounds__(PB) void k_bn_bwd_reduce(long n, int c, const float *__restrict__ gy, const float *__restrict__ x,
+                                                      const float *__restrict__ res, const float *__restrict__ scale,
+                                                      const float *__restrict__ shift, const float *__restrict__ mean,
+                                                      const float *__restrict__ rstd, int relu, float *partial) {
+    extern __shared__ float red[];
+    bn_bwd_reduce_block<RES>(n, c, gy, x, res, scale, shift, mean, rstd, relu, partial, blockIdx.x, gridDim.x, red);
+}
+// two problems in one launch (pdfops_common.h: PdfBnBwd2)
+__global__ __launch_bounds__(PB) void k_bn_bwd_reduce2(PdfBnBwd2 q, int relu) {
+    extern __shared__ float red[];
+    const int i = blockIdx.x >= (unsigned)q.split ? 1 : 0;
+    const float *coef = q.coef[i];
+    const int c = q.c[i];
+    bn_bwd_reduce_block<false>(q.n[i], c, q.gy[i], q.x[i], nullptr, coef, coef + c, coef + 2 * c, coef + 3 * c, relu, q.partial[i],
+                               blockIdx.x - (i ? q.split : 0), i ? gridDim.x - q.split : q.split, red);
 }
 
 // gx = scale * (g' - sums[ch]/n - xhat * sums[c+ch]/n) ; gres = g'
 template <bool RES>
-__global__ __launch_bounds__(PB) void k_bn_bwd_apply(long n4, int c4, const float4 *__restrict__ gy, const float4 *__restrict__ x,
-                                                     const float4 *__restrict__ res, const float4 *__restrict__ scale,
-                                                     const float4 *__restrict__ shift, const float4 *__restrict__ mean,
-                                                     const float4 *__restrict__ rstd, const float4 *__restrict__ sums, float inv_n,
-                                                     int relu, float4 *__restrict__ gx, float4 *__restrict__ gres) {
-    for (long e = (long)blockIdx.x * PB + threadIdx.x; e < n4; e += (long)gridDim.x * PB) {
+__device__ __forceinline__ void bn_bwd_apply_block(long n4, int c4, const float4 *__restrict__ gy, const float4 *__restrict__ x,
+                                                   const float4 *__restrict__ res, const float4 *__restrict__ scale,
+                                                   const float4 *__restrict__ shift, const float4 *__restrict__ mean,
+                                                   const float4 *__restrict__ rstd, const float4 *__restrict__ sums, float inv_n,
+                                                   int relu, float4 *__restrict__ gx, float4 *__restrict__ gres, unsigned block, unsigned nblocks) {
+    for (long e = (long)block * PB + threadIdx.x; e < n4; e += (long)nblocks * PB) {
         const int cc = (int)(e % c4);
         const float4 g4 = gy[e], x4 = x[e], sc = scale[cc], sh = shift[cc], mu = mean[cc], rs = rstd[cc];
         const float4 s1 = sums[cc], s2 = sums[c4 + cc];
@@ -159,6 +177,23 @@ __global__ __launch_bounds__(PB) void k_bn_bwd_apply(long n4, int c4, const floa
         gx[e] = o;
         if (gres) gres[e] = gm;
     }
+}
+template <bool RES>
+__global__ __launch_bounds__(PB) void k_bn_bwd_apply(long n4, int c4, const float4 *__restrict__ gy, const float4 *__restrict__ x,
+                                                     const float4 *__restrict__ res, const float4 *__restrict__ scale,
+                                                     const float4 *__restrict__ shift, const float4 *__restrict__ mean,
+                                                     const float4 *__restrict__ rstd, const float4 *__restrict__ sums, float inv_n,
+                                                     int relu, float4 *__restrict__ gx, float4 *__restrict__ gres) {
+    bn_bwd_apply_block<RES>(n4, c4, gy, x, res, scale, shift, mean, rstd, sums, inv_n, relu, gx, gres, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(PB) void k_bn_bwd_apply2(PdfBnBwd2 q, float inv_n0, float inv_n1, int relu) {
+    const int i = blockIdx.x >= (unsigned)q.split ? 1 : 0;
+    const int c = q.c[i];
+    const float4 *coef = reinterpret_cast<const float4 *>(q.coef[i]);
+    bn_bwd_apply_block<false>(q.n[i] * (c / 4), c / 4, reinterpret_cast<const float4 *>(q.gy[i]), reinterpret_cast<const float4 *>(q.x[i]), nullptr,
+                              coef, coef + c / 4, coef + 2 * (c / 4), coef + 3 * (c / 4), reinterpret_cast<const float4 *>(q.sums[i]),
+                              i ? inv_n1 : inv_n0, relu, reinterpret_cast<float4 *>(q.gx[i]), nullptr,
+                              blockIdx.x - (i ? q.split : 0), i ? gridDim.x - q.split : q.split);
 }
 
 // eval-mode backward: gx = scale * g' (running statistics are constants)
@@ -276,6 +311,70 @@ extern "C" int pdf_bn_coef_from_partial(const float *partial, int rows, long n, 
     fl::launch_bn_finalize(partial, rows, c, (double)n, gamma, beta, eps, momentum, running_mean, running_var, coef, coef + c,
                            coef + 2 * c, coef + 3 * c, static_cast<hipStream_t>(stream));
     return pdf_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Two train-mode BatchNorms at once (pdfops_common.h: the two-problem forms).  Same kernels' bodies, same grids per problem, same bits as
+// two calls of the single entries; one launch instead of two for the finalize, and three instead of six for the backward.
+int pdf_bn_finalize2(PdfBnFinalize2 q, float eps, float momentum, void *stream) {
+    for (int i = 0; i < 2; ++i) {
+        if (!q.partial[i] || q.rows[i] < 1 || q.count[i] < 1.0 || !q.gamma[i] || !q.beta[i] || !q.coef[i]) return PDF_ERR_BAD_ARG;
+        if (!pdf_bn_supported(q.nch[i])) return PDF_ERR_UNSUPPORTED;
+    }
+    fl::launch_bn_finalize2(q, eps, momentum, static_cast<hipStream_t>(stream));
+    return pdf_launch_status();
+}
+// partial[i]: pdf_bn_partial_floats(n[i], c[i]) floats of scratch; sums[i] (2 c) receives [d beta | d gamma]; gx[i] (n, c) the input gradient
+int pdf_bn_backward2(PdfBnBwd2 q, int relu, void *stream) {
+    for (int i = 0; i < 2; ++i) {
+        if (q.n[i] < 1 || !q.gy[i] || !q.x[i] || !q.coef[i] || !q.partial[i] || !q.sums[i] || !q.gx[i]) return PDF_ERR_BAD_ARG;
+        if (!pdf_bn_supported(q.c[i])) return PDF_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int g0 = pw::grid_rows(q.n[0], q.c[0]), g1 = pw::grid_rows(q.n[1], q.c[1]);
+    q.split = g0;
+    pw::k_bn_bwd_reduce2<<<g0 + g1, pw::PB, pw::PB * 8 * sizeof(float), s>>>(q, relu);
+    PdfColsum2 cs;
+    for (int i = 0; i < 2; ++i) { cs.partial[i] = q.partial[i]; cs.rows[i] = i ? g1 : g0; cs.width[i] = 2 * q.c[i]; cs.out[i] = q.sums[i]; }
+    fl::launch_colsum2(cs, s);
+    const int a0 = pw::grid_elems(q.n[0] * (q.c[0] / 4)), a1 = pw::grid_elems(q.n[1] * (q.c[1] / 4));
+    q.split = a0;
+    pw::k_bn_bwd_apply2<<<a0 + a1, pw::PB, 0, s>>>(q, (float)(1.0 / (double)q.n[0]), (float)(1.0 / (double)q.n[1]), relu);
+    return pdf_launch_status();
+}
+
+// C entries of the two (tests compare them with two single calls).  Per problem i, p[6 i + ..]:
+//   pdf_bn_coef_from_partial2: 0 partial rows [rows][2 c] 1 gamma 2 beta 3 running_mean 4 running_var (both or neither null) 5 coef (4 c, written)
+//   pdf_bn_act_backward2     : 0 gy 1 x 2 coef 3 partial (pdf_bn_partial_floats(n, c)) 4 sums (2 c, written) 5 gx (n, c; written)
+extern "C" int pdf_bn_coef_from_partial2(int rows0, long n0, int c0, int rows1, long n1, int c1, void *const *p, float eps, float momentum,
+                                         void *stream) {
+    if (!p || n0 < 1 || n1 < 1) return PDF_ERR_BAD_ARG;
+    PdfBnFinalize2 q;
+    const int rows[2] = {rows0, rows1}, c[2] = {c0, c1};
+    const long n[2] = {n0, n1};
+    for (int i = 0; i < 2; ++i) {
+        void *const *t = p + 6 * i;
+        q.partial[i] = (const float *)t[0]; q.rows[i] = rows[i]; q.nch[i] = c[i]; q.count[i] = (double)n[i];
+        q.gamma[i] = (const float *)t[1]; q.beta[i] = (const float *)t[2]; q.running_mean[i] = (float *)t[3]; q.running_var[i] = (float *)t[4];
+        q.coef[i] = (float *)t[5];
+        if (!t[3] != !t[4]) return PDF_ERR_BAD_ARG;
+    }
+    q.split = 0;
+    return pdf_bn_finalize2(q, eps, momentum, stream);
+}
+extern "C" int pdf_bn_act_backward2(long n0, int c0, long n1, int c1, void *const *p, int relu, void *stream) {
+    if (!p) return PDF_ERR_BAD_ARG;
+    PdfBnBwd2 q;
+    const int c[2] = {c0, c1};
+    const long n[2] = {n0, n1};
+    for (int i = 0; i < 2; ++i) {
+        void *const *t = p + 6 * i;
+        q.n[i] = n[i]; q.c[i] = c[i];
+        q.gy[i] = (const float *)t[0]; q.x[i] = (const float *)t[1]; q.coef[i] = (const float *)t[2];
+        q.partial[i] = (float *)t[3]; q.sums[i] = (float *)t[4]; q.gx[i] = (float *)t[5];
+    }
+    q.split = 0;
+    return pdf_bn_backward2(q, relu, stream);
 }
 
 // y = relu?(x * scale + shift + res) with given coefficients (no statistics pass)

@@ -194,8 +194,6 @@ int try_forward(long n, int k, int o, int nin, int nout, const float *const *x, 
                 int accumulate, float *partial, int mma, hipStream_t s, const float *roww = nullptr, long rws = 0, const float *bx = nullptr,
                 long ldb = 0, const float *bcoef = nullptr, int brelu = 0, int *partial_rows = nullptr, long ldw = 0, void *handoff = nullptr);
 long stats_rows_floats(long n, int o);
-int try_wgrad(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
-              const float *shift, int relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s, const float *roww = nullptr, long rws = 0);
 long wgrad_ws_floats(long n, int k, int o, int ng);
 constexpr int WG_MAXG = 5;   // (as in rowlin2_impl.h)
 struct RArgs {
@@ -203,6 +201,10 @@ struct RArgs {
     float *dW[WG_MAXG], *db[WG_MAXG];
     int B, tiles_k, tiles, otiles, split, K, O;
 };
+int try_wgrad(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
+              const float *shift, int relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s, const float *roww = nullptr, long rws = 0,
+              RArgs *defer = nullptr);   // defer: the slab reduction is not launched, its arguments are handed back
+void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias1, hipStream_t s);
 int try_wgrad_group(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx, const float *const *scale,
                     const float *const *shift, const int *relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s);
 void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s);
@@ -223,6 +225,8 @@ static inline void tiled_wg_plan(long n, int k, int o, int *blocks_oc, long *spl
 static inline bool rowlin_streams(int k, int o) {
     return (k == 32 || k == 64 || k == 128 || k == 256 || k == 512) && o % 16 == 0 && getenv("PDFOPS_ROWLIN_TILED") == nullptr;
 }
+
+int pdf_rowlin_streams(int k, int o) { return rowlin_streams(k, o) ? 1 : 0; }
 
 extern "C" int pdf_rowlin_partial_rows(long n, int k, int o) {
     return rowlin_streams(k, o) ? rl2::stats_rows(n) : (int)((n + rl::BM - 1) / rl::BM);
@@ -341,6 +345,39 @@ extern "C" int pdf_rowlin_wgrad(long n, int k, int o, const float *g, long ldg, 
     r.dW[0] = dw; r.db[0] = db; r.dW[1] = r.dW[2] = nullptr; r.db[1] = r.db[2] = nullptr;
     rl2::launch_slab_reduce(r, 1, db != nullptr, s);
     return pdf_launch_status();
+}
+
+// Two weight gradients of different shapes: the products as in pdf_rowlin_wgrad (rl2::k_wg, one launch each into its own workspace), then
+// ONE launch that reduces the slabs of both (rl2::k_slab_reduce2: each problem with the grid and the lane count of its own reduction --
+// the same sums in the same order).  Three launches instead of four.  Validates everything before the first launch.
+int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream) {
+    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    for (int i = 0; i < 2; ++i) {
+        if (q.n[i] < 1 || q.k[i] < 1 || q.o[i] < 1 || !q.g[i] || !q.x[i] || !q.dw[i] || !q.ws[i]) return PDF_ERR_BAD_ARG;
+        if (!rowlin_streams(q.k[i], q.o[i]) || (q.k[i] % 32) || (q.o[i] % 32)) return PDF_ERR_UNSUPPORTED;
+        if ((reinterpret_cast<uintptr_t>(q.g[i]) | reinterpret_cast<uintptr_t>(q.x[i])) & 15) return PDF_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rl2::RArgs r[2];
+    for (int i = 0; i < 2; ++i) {
+        const float *g = q.g[i];
+        float *dw = q.dw[i], *db = q.db[i];
+        if (!rl2::try_wgrad(q.n[i], q.k[i], q.o[i], 1, &g, q.o[i], q.x[i], q.k[i], nullptr, nullptr, 0, &dw, &db, q.ws[i], mma_input, s, nullptr, 0, &r[i]))
+            return PDF_ERR_UNSUPPORTED;   // (not reached: the conditions of try_wgrad are checked above)
+    }
+    rl2::launch_slab_reduce2(r[0], q.db[0] != nullptr, r[1], q.db[1] != nullptr, s);
+    return pdf_launch_status();
+}
+// p[]: per problem i, p[5 i + ..]: 0 g (n, o) 1 x (n, k) 2 dW (o, k; written) 3 db (o; written) or null 4 ws (pdf_rowlin_wgrad_ws_floats(n, k, o, 1))
+extern "C" int pdf_rowlin_wgrad2(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, int mma_input, void *stream) {
+    if (!p) return PDF_ERR_BAD_ARG;
+    PdfWgrad2 q;
+    q.n[0] = n0; q.k[0] = k0; q.o[0] = o0; q.n[1] = n1; q.k[1] = k1; q.o[1] = o1;
+    for (int i = 0; i < 2; ++i) {
+        void *const *t = p + 5 * i;
+        q.g[i] = (const float *)t[0]; q.x[i] = (const float *)t[1]; q.dw[i] = (float *)t[2]; q.db[i] = (float *)t[3]; q.ws[i] = (float *)t[4];
+    }
+    return pdf_rowlin_wgrad_pair(q, mma_input, stream);
 }
 
 // Several Linear layers over the same rows in one launch (channel widths 32..256, see rowlin2.hip):

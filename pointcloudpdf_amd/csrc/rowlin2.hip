@@ -8,7 +8,7 @@ template int try_forward_mp<0>(long, int, int, int, int, const float *const *, l
                                const float *, int, float *const *, long, int, float *, hipStream_t, const float *, long, const float *, long,
                                const float *, int, int *, long, void *);
 template int try_wgrad_mp<0>(long, int, int, int, const float *const *, long, const float *, long, const float *, const float *, int,
-                             float *const *, float *const *, float *, hipStream_t, const float *, long);
+                             float *const *, float *const *, float *, hipStream_t, const float *, long, RArgs *);
 template int try_wgrad_group_mp<0>(long, int, int, int, const float *const *, long, const float *const *, long, const float *const *, const float *const *, const int *,
                                    float *const *, float *const *, float *, hipStream_t);
 extern template int try_wgrad_group_mp<1>(long, int, int, int, const float *const *, long, const float *const *, long, const float *const *, const float *const *, const int *,
@@ -22,9 +22,9 @@ extern template int try_forward_mp<2>(long, int, int, int, int, const float *con
                                       const float *, int, float *const *, long, int, float *, hipStream_t, const float *, long, const float *, long,
                                       const float *, int, int *, long, void *);
 extern template int try_wgrad_mp<1>(long, int, int, int, const float *const *, long, const float *, long, const float *, const float *, int,
-                                    float *const *, float *const *, float *, hipStream_t, const float *, long);
+                                    float *const *, float *const *, float *, hipStream_t, const float *, long, RArgs *);
 extern template int try_wgrad_mp<2>(long, int, int, int, const float *const *, long, const float *, long, const float *, const float *, int,
-                                    float *const *, float *const *, float *, hipStream_t, const float *, long);
+                                    float *const *, float *const *, float *, hipStream_t, const float *, long, RArgs *);
 
 // returns 1 when a streaming kernel took the job, 0 when the shape is not covered (caller falls back to the tiled kernel)
 int try_forward(long n, int k, int o, int nin, int nout, const float *const *x, long ldx, const float *const *w, int transpose_w,
@@ -42,11 +42,12 @@ int try_forward(long n, int k, int o, int nin, int nout, const float *const *x, 
 }
 
 int try_wgrad(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
-              const float *shift, int relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s, const float *roww, long rws) {
+              const float *shift, int relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s, const float *roww, long rws,
+              RArgs *defer) {
     switch (mma) {
-    case 1: return try_wgrad_mp<1>(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, s, roww, rws);
-    case 2: return try_wgrad_mp<2>(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, s, roww, rws);
-    default: return try_wgrad_mp<0>(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, s, roww, rws);
+    case 1: return try_wgrad_mp<1>(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, s, roww, rws, defer);
+    case 2: return try_wgrad_mp<2>(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, s, roww, rws, defer);
+    default: return try_wgrad_mp<0>(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, s, roww, rws, defer);
     }
 }
 

@@ -6,7 +6,7 @@ template int try_forward_mp<1>(long, int, int, int, int, const float *const *, l
                                const float *, int, float *const *, long, int, float *, hipStream_t, const float *, long, const float *, long,
                                const float *, int, int *, long, void *);
 template int try_wgrad_mp<1>(long, int, int, int, const float *const *, long, const float *, long, const float *, const float *, int,
-                             float *const *, float *const *, float *, hipStream_t, const float *, long);
+                             float *const *, float *const *, float *, hipStream_t, const float *, long, RArgs *);
 template int try_wgrad_group_mp<1>(long, int, int, int, const float *const *, long, const float *const *, long, const float *const *, const float *const *, const int *,
                                    float *const *, float *const *, float *, hipStream_t);
 }  // namespace rl2

@@ -558,18 +558,20 @@ struct RArgs {
     int B, tiles_k, tiles, otiles, split, K, O;
 };
 void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s);
-template <int L>
-__global__ __launch_bounds__(64 * L) void k_slab_reduce(RArgs a) {
-    __shared__ float red[L][64];
-    const int e = threadIdx.x & 63, l = threadIdx.x >> 6, z = blockIdx.z;
-    const int ei = blockIdx.x * 64 + e;
-    const bool bias = (int)blockIdx.y >= a.tiles;
-    const int t = bias ? (int)blockIdx.y - a.tiles : (int)blockIdx.y;
+void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias1, hipStream_t s);
+// One workgroup of the reduction: (bx, by, z) = its block id in the grid of ITS problem; lanes 64 L and above of a wider workgroup (the
+// two-problem launch, whose problems may differ in L) only take part in the barrier.
+template <int L, bool WIDE>
+__device__ __forceinline__ void slab_reduce_block(const RArgs &a, int bx, int by, int z, float (*red)[64]) {
+    const int e = threadIdx.x & 63, l = threadIdx.x >> 6;
+    const int ei = bx * 64 + e;
+    const bool bias = by >= a.tiles;
+    const int t = bias ? by - a.tiles : by;
     const int len = bias ? a.B : a.B * a.B;
-    if (bias && (int)blockIdx.x * 64 >= len) return;   // (uniform per block)
+    if (bias && bx * 64 >= len) return;   // (uniform per block)
     const float *src = bias ? a.bslab + ((size_t)z * a.otiles + t) * a.split * a.B : a.slab + ((size_t)z * a.tiles + t) * a.split * (size_t)(a.B * a.B);
     float s = 0.f;
-    if (ei < len) {
+    if (ei < len && (!WIDE || l < L)) {
         int k = l;
         for (; k + 3 * L < a.split; k += 4 * L) {   // four loads in flight per lane
             const float v0 = src[(size_t)k * len + ei], v1 = src[(size_t)(k + L) * len + ei];
@@ -591,6 +593,27 @@ __global__ __launch_bounds__(64 * L) void k_slab_reduce(RArgs a) {
         if (o < a.O && kk < a.K) a.dW[z][(size_t)o * a.K + kk] = s;
     }
 }
+template <int L>
+__global__ __launch_bounds__(64 * L) void k_slab_reduce(RArgs a) {
+    __shared__ float red[L][64];
+    slab_reduce_block<L, false>(a, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, red);
+}
+static inline int slab_reduce_lanes(int split) { return split > 32 ? 16 : (split > 4 ? 4 : 1); }   // L of a reduction over `split` slabs
+
+// Two single-gradient reductions in ONE launch: grid rows below `ysplit` are problem 0's grid, the rest problem 1's.  Each problem is
+// summed with the L (and so the order) of its own launch; the workgroup is as wide as the larger L needs.
+struct RArgs2 { RArgs a[2]; int L[2], gx[2], ysplit; };
+template <int LMAX>
+__global__ __launch_bounds__(64 * LMAX) void k_slab_reduce2(RArgs2 q) {
+    __shared__ float red[LMAX][64];
+    const int i = (int)blockIdx.y >= q.ysplit ? 1 : 0;
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y - (i ? q.ysplit : 0);
+    if (bx >= q.gx[i]) return;   // (uniform per block: the x extent is the larger of the two)
+    const int L = q.L[i];
+    if (LMAX >= 16 && L == 16) slab_reduce_block<16, true>(q.a[i], bx, by, 0, red);
+    else if (LMAX >= 4 && L == 4) slab_reduce_block<4, true>(q.a[i], bx, by, 0, red);
+    else slab_reduce_block<1, true>(q.a[i], bx, by, 0, red);
+}
 
 #ifdef RL2_MAIN_TU
 void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s) {
@@ -598,6 +621,23 @@ void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s) {
     if (a.split > 32) k_slab_reduce<16><<<grid, 64 * 16, 0, s>>>(a);
     else if (a.split > 4) k_slab_reduce<4><<<grid, 64 * 4, 0, s>>>(a);
     else k_slab_reduce<1><<<grid, 64, 0, s>>>(a);
+}
+void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias1, hipStream_t s) {
+    RArgs2 q;
+    q.a[0] = a0; q.a[1] = a1;
+    const bool bias[2] = {bias0, bias1};
+    int gy[2];
+    for (int i = 0; i < 2; ++i) {
+        q.L[i] = slab_reduce_lanes(q.a[i].split);
+        q.gx[i] = (q.a[i].B * q.a[i].B + 63) / 64;
+        gy[i] = q.a[i].tiles + (bias[i] ? q.a[i].otiles : 0);
+    }
+    q.ysplit = gy[0];
+    const dim3 grid((unsigned)std::max(q.gx[0], q.gx[1]), (unsigned)(gy[0] + gy[1]), 1u);
+    const int lmax = std::max(q.L[0], q.L[1]);
+    if (lmax == 16) k_slab_reduce2<16><<<grid, 64 * 16, 0, s>>>(q);
+    else if (lmax == 4) k_slab_reduce2<4><<<grid, 64 * 4, 0, s>>>(q);
+    else k_slab_reduce2<1><<<grid, 64, 0, s>>>(q);
 }
 #endif
 
@@ -757,7 +797,8 @@ int try_forward_mp(long n, int k, int o, int nin, int nout, const float *const *
 
 template <int MP>
 int try_wgrad_mp(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
-                 const float *shift, int relu, float *const *dw, float *const *db, float *ws, hipStream_t s, const float *roww, long rws) {
+                 const float *shift, int relu, float *const *dw, float *const *db, float *ws, hipStream_t s, const float *roww, long rws,
+                 RArgs *defer) {   // defer: the slab reduction is not launched, its arguments are handed back (launch_slab_reduce2)
     if (ng < 1 || ng > 3 || !ws) return 0;
     const WgPlan p = wg_plan(n, k, o, ng);
     const int vw = p.vw;
@@ -787,7 +828,8 @@ int try_wgrad_mp(long n, int k, int o, int ng, const float *const *g, long ldg, 
     RArgs r;
     r.slab = a.slab; r.bslab = a.bslab; r.B = b; r.tiles_k = k / b; r.tiles = (o / b) * (k / b); r.otiles = o / b; r.split = (int)p.split; r.K = k; r.O = o;
     for (int i = 0; i < WG_MAXG; ++i) { r.dW[i] = a.dW[i]; r.db[i] = a.db[i]; }
-    launch_slab_reduce(r, ng, any_bias, s);
+    if (defer) *defer = r;
+    else launch_slab_reduce(r, ng, any_bias, s);
     return 1;
 }
 

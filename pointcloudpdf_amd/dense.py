@@ -831,3 +831,97 @@ def linear_bn_act(lin, bn, x, relu):
     if bn.training:
         bump_counters([bn.num_batches_tracked])
     return y
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The two-input TransitionUp, relu(bn1(linear1(x1))) + interpolation(relu(bn2(linear2(x2)))), as one autograd node and one host call per
+# direction (csrc/block.hip: pdf_transition_up_*): 4 + 9 launches instead of the 8 + 13 of two _LinBnFn nodes, the interpolation and
+# the add; the normalised activations and the interpolated tensor never reach memory.  Same bits as the composed path.
+# ------------------------------------------------------------------------------------------------------------------
+class _TransitionUpFn(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, bn1, bn2, idx, weight, x1, W1, b1, g1, be1, x2, W2, b2, g2, be2):
+        from . import _native
+
+        be = _be()
+        _rcd(x1, x2, W1, W2, idx, weight)
+        lib = be.lib
+        (n1, k1), (n2, k2), o = x1.shape, x2.shape, W1.shape[0]
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x1.device)
+        z1, coef1, z2, coef2, out = e(n1, o), e(4 * o), e(n2, o), e(4 * o), e(n1, o)
+        part1, part2 = e(int(lib.pdf_rowlin_partial_floats(n1, o))), e(int(lib.pdf_rowlin_partial_floats(n2, o)))
+        order = _native.order_of(idx)
+        P = lambda t: None if t is None else t.data_ptr()
+        ptrs = [P(x1), P(W1), P(b1), P(g1), P(be1), P(bn1.running_mean), P(bn1.running_var),
+                P(x2), P(W2), P(b2), P(g2), P(be2), P(bn2.running_mean), P(bn2.running_var),
+                P(idx), P(weight), P(order), P(z1), P(coef1), P(part1), P(z2), P(coef2), P(part2), P(out)]
+        rc = lib.pdf_transition_up_forward(n1, k1, n2, k2, o, (c_void_p * len(ptrs))(*ptrs), 1, ctypes.c_float(bn1.eps), ctypes.c_float(bn1.momentum),
+                                           _mma(), be._stream())
+        if rc != 0:
+            raise RuntimeError(f"pdf_transition_up_forward failed with status {rc}")
+        ctx.save_for_backward(x1, z1, coef1, W1, x2, z2, coef2, W2, idx, weight)
+        ctx.has_bias = (b1 is not None, b2 is not None)
+        return out
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g):
+        from . import _native
+
+        x1, z1, coef1, W1, x2, z2, coef2, W2, idx, weight = ctx.saved_tensors
+        be = _be()
+        lib = be.lib
+        (n1, k1), (n2, k2), o = x1.shape, x2.shape, W1.shape[0]
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x1.device)
+        need1, need2 = ctx.needs_input_grad[4], ctx.needs_input_grad[9]
+        gx1 = e(n1, k1) if need1 else None
+        gx2 = e(n2, k2) if need2 else None
+        grads1, grads2 = e(o * k1 + 3 * o), e(o * k2 + 3 * o)
+        g2, gz1, gz2 = e(n2, o), e(n1, o), e(n2, o)
+        part1, part2 = e(int(lib.pdf_bn_partial_floats(n1, o))), e(int(lib.pdf_bn_partial_floats(n2, o)))
+        ws1, ws2 = be.wgrad_workspace(n1, k1, o, 1, x1.device), be.wgrad_workspace(n2, k2, o, 1, x1.device)
+        g = g.contiguous()
+        inv_off, inv_entry, entry_base = _native.inverse_table(idx, n2)   # (the table and source order interpolation_backward uses)
+        src_order = _native.src_order_of(idx, n2)
+        P = lambda t: None if t is None else t.data_ptr()
+        ptrs = [P(g), P(x1), P(z1), P(coef1), P(W1), P(x2), P(z2), P(coef2), P(W2), P(weight), P(inv_off), P(inv_entry), P(src_order),
+                P(gx1), P(gx2), P(grads1), P(grads2), P(g2), P(gz1), P(gz2), P(part1), P(part2), P(ws1), P(ws2)]
+        rc = lib.pdf_transition_up_backward(n1, k1, n2, k2, o, (c_void_p * len(ptrs))(*ptrs), int(entry_base), _mma(), be._stream())
+        if rc != 0:
+            raise RuntimeError(f"pdf_transition_up_backward failed with status {rc}")
+
+        def split(grads, k, has_bias):   # buffer: dW | db | dbeta | dgamma -> dW, db, dgamma, dbeta
+            ok = o * k
+            return grads[:ok].view(o, k), grads[ok:ok + o] if has_bias else None, grads[ok + 2 * o:ok + 3 * o], grads[ok + o:ok + 2 * o]
+
+        return (None, None, None, None, gx1, *split(grads1, k1, ctx.has_bias[0]), gx2, *split(grads2, k2, ctx.has_bias[1]))
+
+
+TUFUSED = True   # module-wide switch of the TransitionUp node (tests compare both paths)
+
+
+def tu_ok(lin1, bn1, lin2, bn2, x1, x2, idx, weight):
+    """The node takes the join when both Linear -> BatchNorm1d pairs would take ``_LinBnFn`` in training mode, the (n1, 3) tables are
+    device tensors of the kNN pass and the backend scatters through inverse tables (what the node's backward walks)."""
+    if not (TUFUSED and linbn_ok(lin1, bn1, x1) and linbn_ok(lin2, bn2, x2)):
+        return False
+    if not (bn1.training and bn2.training and bn1.eps == bn2.eps and bn1.momentum == bn2.momentum and lin1.out_features == lin2.out_features):
+        return False
+    if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.shape[1] == 3 and idx.is_contiguous() and idx.shape[0] == x1.shape[0]
+            and weight.is_cuda and weight.dtype == torch.float32 and weight.shape == idx.shape and weight.is_contiguous()):
+        return False
+    if x1.shape[0] < 1 or x2.shape[0] < 1 or any(p.dtype != torch.float32 or not p.is_contiguous() for p in (lin1.weight, lin2.weight)):
+        return False
+    from . import _native
+
+    be = _be()
+    if _native.backend_for(x1) is not be or not getattr(be, "use_inverse", False):
+        return False
+    return bool(be.lib.pdf_transition_up_supported(lin1.in_features, lin2.in_features, lin1.out_features))
+
+
+def transition_up(lin1, bn1, lin2, bn2, x1, x2, idx, weight):
+    out = _TransitionUpFn.apply(bn1, bn2, idx, weight, x1, lin1.weight, lin1.bias, bn1.weight, bn1.bias, x2, lin2.weight, lin2.bias, bn2.weight, bn2.bias)
+    bump_counters([bn1.num_batches_tracked, bn2.num_batches_tracked])
+    return out

@@ -320,6 +320,22 @@ class TransitionUp(nn.Module):
         ends = tag[0].offset_host(tag[1]) if tag is not None else [int(v) for v in o.detach().cpu().tolist()]
         return [ends[0]] + [ends[i] - ends[i - 1] for i in range(1, len(ends))]
 
+    def _join_fused(self, p1, x1, o1, p2, x2, o2):
+        """The two-input form as one node (dense.transition_up), or None where the composed ops apply (CPU oracle, eval, fp64 probes,
+        other widths)."""
+        l1, l2 = self.linear1, self.linear2
+        if not (dense.TUFUSED and len(l1) == 3 and len(l2) == 3 and x1.is_cuda and x1.dtype == torch.float32 and x2.dtype == torch.float32
+                and x1.dim() == 2 and x2.dim() == 2 and isinstance(l1[0], nn.Linear) and isinstance(l2[0], nn.Linear)
+                and isinstance(l1[2], nn.ReLU) and isinstance(l2[2], nn.ReLU) and p1.is_contiguous() and p2.is_contiguous()
+                and l1[1].training and l2[1].training and dense.linbn_ok(l1[0], l1[1], x1) and dense.linbn_ok(l2[0], l2[1], x2)):
+            return None   # (decided before the tables are asked for: the composed path asks for them itself)
+        from .pointops import _ops
+
+        idx, weight = _ops._interp_tables(p2, p1, o2, o1, 3)
+        if not dense.tu_ok(l1[0], l1[1], l2[0], l2[1], x1, x2, idx, weight):
+            return None
+        return dense.transition_up(l1[0], l1[1], l2[0], l2[1], x1, x2, idx, weight)
+
     def forward(self, pxo1, pxo2=None):
         if pxo2 is None:
             p, x, o = pxo1  # head: append the scene-mean context to every point (:148-161)
@@ -333,7 +349,9 @@ class TransitionUp(nn.Module):
         else:
             p1, x1, o1 = pxo1
             p2, x2, o2 = pxo2
-            x = _seq(self.linear1, x1) + pointops.interpolation(p2, p1, _seq(self.linear2, x2), o2, o1)
+            x = self._join_fused(p1, x1, o1, p2, x2, o2)
+            if x is None:
+                x = _seq(self.linear1, x1) + pointops.interpolation(p2, p1, _seq(self.linear2, x2), o2, o1)
         return x
 
 
