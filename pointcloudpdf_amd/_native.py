@@ -12,6 +12,8 @@ import threading
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PDFOPS_DIST_FMA=1|2: the library whose geometry kernels (kNN, ball query, FPS) evaluate the squared distance as an explicit FMA
 # chain -- the arithmetic an `nvcc -O2` build of libs/pointops most likely runs (csrc/pdfops_common.h: pdf_sqdist3).
@@ -26,157 +28,10 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 19   # include/pdfops.h: PDF_ABI_VERSION (the argtypes below are THIS version's parameter lists)
+ABI_VERSION = 19   # include/pdfops.h: PDF_ABI_VERSION (the rows of _abi.ENTRIES are THIS version's parameter lists)
 
 c_int = ctypes.c_int
-c_long = ctypes.c_long
 c_void_p = ctypes.c_void_p
-c_float = ctypes.c_float
-c_double = ctypes.c_double
-
-# name -> argument kinds ("i" int, "l" long, "f" float, "p" pointer); the stream pointer is appended for HIP.
-_PROTOS = {
-    "knn_query": "iippppipp",
-    "ball_query": "iiffppppipp",
-    "random_ball_query": "iiffpppppipp",
-    "farthest_point_sampling": "iippppp",
-    "grouping_forward": "iiippp",
-    "grouping_backward": "iiippp",
-    "interpolation_forward": "iiipppp",
-    "interpolation_backward": "iiipppp",
-    "subtraction_forward": "iiipppp",
-    "subtraction_backward": "iiipppp",
-    "aggregation_forward": "iiiippppp",
-    "aggregation_backward": "iiiipppppppp",
-    "attention_relation_step_forward": "iiipppppp",
-    "attention_relation_step_backward": "iiippppppppp",
-    "attention_fusion_step_forward": "iiippppp",
-    "attention_fusion_step_backward": "iiippppppp",
-    # libs/pointops2 window attention (v2 / v3 launchers)
-    "attention_step1_forward_v2": "iiiiippppp",
-    "attention_step1_backward_v2": "iiiiippppppp",
-    "dot_prod_with_idx_forward_v3": "iiiiipppppppp",
-    "dot_prod_with_idx_backward_v3": "iiiiipppppppppppp",
-    "attention_step2_with_rel_pos_value_forward_v2": "iiiiippppppp",
-    "attention_step2_with_rel_pos_value_backward_v2": "iiiiipppppppppp",
-    "segment_softmax_forward": "iiippp",
-    "segment_softmax_backward": "iiipppp",
-}
-_HIP_ONLY_PROTOS = {
-    "grid_hash": "lippdddippp",
-    "grid_hash_f64": "lippdddppp",
-    "philox4x64": "llllp",
-    "aug_bounds": "ippppp",
-    "aug_points": "ilpipppppp",
-    "aug_keys": "ilpplp",
-    "aug_elastic_noise": "ilpplp",
-    "aug_elastic_blur": "ilpppi",
-    "aug_elastic_apply": "ilpppppdpp",
-    "radius_neighbors_self": "iifppipppl",
-    "radius_neighbors_self_adaptive": "iiffppippppl",
-    "vote_accumulate": "lipppppp",
-    "fragment_bounds": "lliiipppppp",
-    "fragment_gather": "lliiipppppipppppppp",
-    "fragment_vote": "lliiippppppppp",
-    "graph_forest": "lipppppipppl",
-    "gmm2_1d": "ipppidd",
-    "dot_prod_with_idx_forward_v3_l": "iiiiipppppppp",
-    "dot_prod_with_idx_backward_v3_l": "iiiiipppppppppppp",
-    "attention_step2_with_rel_pos_value_backward_v2_l": "iiiiipppppppppp",
-    "scene_sum_rows": "ipiplip",
-    "scene_repeat_rows": "iplipip",
-    "region_stats": "ippppifppp",
-    "region_seeds": "ippppip",
-    "region_grow": "ippipppipiipppp",
-    "region_edges": "ipppppippppppppppppl",
-    "sort_floats_dev": "ipppppp",
-    "gmm2_weak_dev": "ippppppppidd",
-    "region_mask": "ippppppp",
-    "region_tree": "ippipppppppp",
-    "graph_forest_dev": "lipppppippppl",
-    "gmm2_1d_dev": "ippppidd",
-    "graph_forest_batch_dev": "ippippppppipppl",
-    "wa_segment_rows": "iiiipppppplfpplf",
-    "wa_segment_rows_ordered": "iiiipppppplfpplfp",
-    "wa_table_grad": "iiiippppplfpp",
-    "wa_grad_attn": "iiiiiplppplppp",
-    "wa_logits_forward": "iiiiipplfpppppp",
-    "wa_permute_edges": "iippp",
-    "wa_logits_forward_ordered": "iiiiipplfppppppp",
-    "wa_grad_attn_ordered": "iiiiiplppplpppp",
-    "window_keys": "ippippfippp",
-    "window_keys_scene": "ippippfippp",
-    "scene_bounds": "ippipp",
-    "window_edges_count": "ippipppppp",
-    "window_edges_fill": "ipppppppffipppp",
-    "group_forward": "iiiippppp",
-    "group_backward": "iiiippp",
-    "interpolation_weights": "iipp",
-    "farthest_point_sampling_bucketed": "iiipppplp",
-    "grouping_forward_ordered": "iiipppp",
-    "group_forward_ordered": "iiiipppppp",
-    "interpolation_forward_ordered": "iiippppp",
-    "subtraction_forward_ordered": "iiippppp",
-    "aggregation_forward_ordered": "iiiipppppp",
-    "seg_sum_rows": "lipppifp",
-    "seg_sum_rows_strided": "liplppifp",
-    "seg_sum_rows_own": "liipppifppp",
-    "seg_sum_weighted": "liiippppip",
-    "seg_sum_weighted_ordered": "liiippppipp",
-    # csrc/criteria.hip
-    "ce_ex_forward": "lipppfilppp",
-    "ce_ex_backward": "lipppip",
-    "focal_forward": "lipppffilppp",
-    "focal_backward": "lipppp",
-    "dice_forward": "lippfflppp",
-    "dice_backward": "lipplfppp",
-    "bfocal_forward": "lppffiippp",
-    "bfocal_backward": "lpppip",
-    # csrc/grid_pool.hip, csrc/gva.hip
-    "grid_pool_partition": "lppippfppppp",
-    "grid_pool_reduce": "llippppppp",
-    "grid_pool_max_backward": "llipppp",
-    "grid_unpool_forward": "llippp",
-    "gva_relation_forward": "lliipppppp",
-    "gva_relation_backward": "llii" + "p" * 10,
-    "gva_attend_forward": "lliii" + "p" * 6,
-    "gva_attend_backward": "lliii" + "p" * 10,
-    # csrc/cac.hip
-    "cac_soft_proto_forward": "liiipppfppp",
-    "cac_soft_proto_backward": "liiipppfppppp",
-    "cac_label_proto_forward": "liipppppp",
-    "cac_label_proto_backward": "liipppp",
-    "cac_cosine_forward": "liiipppfp",
-    "cac_cosine_backward": "liiipppfpppp",
-    "cac_distill_forward": "lipppfpppp",
-    "cac_distill_backward": "lippppp",
-    # csrc/sparse_conv.hip
-    "spconv_sort_sites": "lppppp",
-    "spconv_subm_table": "lppppip",
-    "spconv_down": "l" + "p" * 13,
-    "spconv_gather": "llliiippippplllpp",
-    "spconv_small_forward": "liiippppp",
-    "spconv_small_dgrad": "liiipppp",
-    "spconv_wgrad": "lliiipppipp",
-    "spconv_colsum": "lippp",
-    # csrc/serialization.hip, csrc/serial_attention.hip
-    "serial_codes": "liiippp",
-    "serial_sort": "lipppp",
-    "serial_pool_partition": "lipppppppp",
-    "serial_attn_forward": "liifpppipp",
-    "serial_attn_backward": "liifppppppipipp",
-    # csrc/point_group.hip
-    "pg_ball_count": "iifpppppl",
-    "pg_ball_fill": "iifppplppl",
-    "pg_cluster_labels": "ipplpi" + "p" * 7,
-    "pg_cluster_fill": "llppp",
-    "pg_proposals_select": "ipippp",
-    "pg_proposals_fill": "ililpppppl" + "p" * 7,
-    "pg_intersections": "llii" + "p" * 7,
-    "pg_bias_loss_forward": "lpppiplpppp",
-    "pg_bias_loss_backward": "lppppip",
-}
-_KIND = {"i": c_int, "l": c_long, "f": c_float, "d": c_double, "p": c_void_p}
 
 
 class PdfOpsError(RuntimeError):
@@ -217,7 +72,7 @@ def cu_masked_stream(first_cu, n_cus, device=None):
     with torch.cuda.device(dev):
         rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(handle), ctypes.c_uint32(words), mask)
     if rc != 0:
-        raise PdfOpsError(f"hipExtStreamCreateWithCUMask failed with status {rc}")
+        raise PdfOpsError(f"hipExtStreamCreateWithCUMask returned hipError {rc}")
     return torch.cuda.ExternalStream(handle.value, device=torch.device("cuda", dev))
 
 
@@ -370,20 +225,14 @@ class CBackend:
     overwrites_outputs = False
 
     def __init__(self, lib, prefix, device_type, use_stream, extra_protos=(), proto_overrides=None):
+        """Binds the reference launchers and the short names in ``extra_protos`` (None: every row of the table) from ``_abi.ENTRIES``;
+        ``proto_overrides``: short name -> the kinds of a launcher whose parameter list differs in ``lib``."""
         self.lib = lib
         self.prefix = prefix
         self.device_type = device_type
         self.use_stream = use_stream
-        self._fn = {}
-        protos = dict(_PROTOS)
-        for k in extra_protos:
-            protos[k] = _HIP_ONLY_PROTOS[k]
-        protos.update(proto_overrides or {})
-        for name, kinds in protos.items():
-            f = getattr(lib, prefix + name)
-            f.restype = c_int
-            f.argtypes = [_KIND[k] for k in kinds] + ([c_void_p] if use_stream else [])
-            self._fn[name] = f
+        names = None if extra_protos is None else _abi.REFERENCE_OPS + tuple(extra_protos)
+        self._fn = _abi.bind(lib, names, prefix, use_stream, proto_overrides)
 
     # -- plumbing -------------------------------------------------------------------------------
     def _ptr(self, t):
@@ -392,9 +241,20 @@ class CBackend:
                 f"pointcloudpdf_amd: tensor on '{t.device}' but this backend runs on '{self.device_type}' "
                 "(the HIP path has no CPU fallback)"
             )
-        return c_void_p(t.data_ptr())
+        return t.data_ptr()
+
+    def _launch(self, name, *args, unsupported_ok=False):
+        """The one launch path: ``args`` are raw already (ints, floats, None, ``data_ptr()`` integers, ctypes arrays; the prototype
+        converts them), the current stream is appended, a non-zero status raises.  No per-argument work and no device check: a
+        caller that takes tensors of any device goes through ``_call``, one that must not calls ``require_current_device`` first.
+        ``unsupported_ok``: PDF_ERR_UNSUPPORTED (-3) is returned instead, for the callers that have another path for the shape."""
+        rc = self._fn[name](*args, raw_stream()) if self.use_stream else self._fn[name](*args)
+        if rc != 0 and not (unsupported_ok and rc == -3):
+            raise PdfOpsError(f"{self.prefix}{name} failed with status {rc}")
+        return rc
 
     def _call(self, name, *args):
+        """``_launch`` on tensors: every tensor becomes its pointer, and the launch goes to the tensors' device."""
         conv, dev = [], None
         for a in args:
             if isinstance(a, torch.Tensor):
@@ -405,17 +265,12 @@ class CBackend:
                     raise PdfOpsError(f"{self.prefix}{name}: tensors on different devices ({dev}, {a.device})")
             else:
                 conv.append(a)
-        if self.use_stream:
-            if dev is not None and dev.index != torch.cuda.current_device():
-                # the stream must belong to the tensors' device (and per-device kernel attributes are set for the current one)
-                with torch.cuda.device(dev):
-                    rc = self._fn[name](*conv, c_void_p(raw_stream()))
-            else:
-                rc = self._fn[name](*conv, c_void_p(raw_stream()))
+        if self.use_stream and dev is not None and dev.index != torch.cuda.current_device():
+            # the stream must belong to the tensors' device (and per-device kernel attributes are set for the current one)
+            with torch.cuda.device(dev):
+                self._launch(name, *conv)
         else:
-            rc = self._fn[name](*conv)
-        if rc != 0:
-            raise PdfOpsError(f"{self.prefix}{name} failed with status {rc}")
+            self._launch(name, *conv)
 
     def _new(self, like, shape, dtype, zero=False):
         return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=like.device)
@@ -676,236 +531,17 @@ class HipBackend(CBackend):
     overwrites_outputs = True
 
     def __init__(self, lib):
-        super().__init__(lib, "pdf_", "cuda", True, extra_protos=tuple(_HIP_ONLY_PROTOS))
-        lib.pdf_fps_workspace_bytes.restype = c_long
-        lib.pdf_fps_workspace_bytes.argtypes = [c_int, c_int]
-        lib.pdf_wa_table_grad_ws_floats.restype = c_long
-        lib.pdf_wa_table_grad_ws_floats.argtypes = [c_int, c_int, c_int]
-        lib.pdf_layernorm_supported.restype = c_int
-        lib.pdf_layernorm_supported.argtypes = [c_int]
-        lib.pdf_layernorm_partial_floats.restype = c_long
-        lib.pdf_layernorm_partial_floats.argtypes = [c_long, c_int]
-        lib.pdf_layernorm_forward.restype = c_int
-        lib.pdf_layernorm_forward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_layernorm_backward.restype = c_int
-        lib.pdf_layernorm_backward.argtypes = [c_long, c_int] + [c_void_p] * 10
-        lib.pdf_fps_stats_offset.restype = c_long
-        lib.pdf_fps_stats_offset.argtypes = [c_int, c_int]
-        self.collect_fps_stats = False  # debug: keep the work counters of the last bucketed FPS call (forces a sync)
-        self.last_fps_stats = None
-        lib.pdf_aug_bounds_workspace_doubles.restype = c_int
-        lib.pdf_aug_bounds_workspace_doubles.argtypes = [c_int]
-        lib.pdf_fragment_bounds_ws_doubles.restype = c_long
-        lib.pdf_fragment_bounds_ws_doubles.argtypes = [c_int]
-        lib.pdf_abi_version.restype = c_int
-        lib.pdf_build_info.restype = ctypes.c_char_p
-        lib.pdf_pg_ball_workspace_bytes.restype = c_long
-        lib.pdf_pg_ball_workspace_bytes.argtypes = [c_int, c_int]
-        lib.pdf_pg_bias_loss_workspace_doubles.restype = c_long
-        lib.pdf_pg_bias_loss_workspace_doubles.argtypes = []
+        _abi.bind(lib, ("abi_version",))   # first, alone: a stale library may lack a symbol that a later row names
         got = int(lib.pdf_abi_version())
         if got != ABI_VERSION:   # parameter lists differ between versions: calling through would hand shifted arguments to the kernels
             raise PdfOpsError(f"libpdfops ABI {got} != {ABI_VERSION} expected by pointcloudpdf_amd/_native.py (include/pdfops.h: PDF_ABI_VERSION): "
                               "stale library -- rebuild with `python -m pointcloudpdf_amd.build --force`")
-        for nm in ("pre_forward", "post_forward"):
-            f = getattr(lib, "pdf_block_" + nm)
-            f.restype = c_int
-            f.argtypes = [c_long, c_int, c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
-        lib.pdf_td_tables.restype = c_int
-        lib.pdf_td_tables.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
-                                      c_int, c_void_p]
-        lib.pdf_td_supported.restype = c_int
-        lib.pdf_td_supported.argtypes = [c_int, c_int, c_int]
-        lib.pdf_td_gram_floats.restype = c_long
-        lib.pdf_td_gram_floats.argtypes = [c_int]
-        lib.pdf_td_fwd_scratch_floats.restype = c_long
-        lib.pdf_td_fwd_scratch_floats.argtypes = [c_long, c_int]
-        lib.pdf_td_bwd_scratch_floats.restype = c_long
-        lib.pdf_td_bwd_scratch_floats.argtypes = [c_long, c_int, c_int]
-        lib.pdf_td_forward.restype = c_int
-        lib.pdf_td_forward.argtypes = [c_long, c_long, c_int, c_int, c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
-        lib.pdf_td_backward.restype = c_int
-        lib.pdf_td_backward.argtypes = [c_long, c_long, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
-        lib.pdf_ce_workspace_floats.restype = c_long
-        lib.pdf_ce_workspace_floats.argtypes = []
-        lib.pdf_ce_forward.restype = c_int
-        lib.pdf_ce_forward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_ce_backward.restype = c_int
-        lib.pdf_ce_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_criteria_workspace_floats.restype = c_long
-        lib.pdf_criteria_workspace_floats.argtypes = [c_int]
-        lib.pdf_cac_supported.restype = c_int
-        lib.pdf_cac_supported.argtypes = [c_int, c_int]
-        lib.pdf_cac_workspace_floats.restype = c_long
-        lib.pdf_cac_workspace_floats.argtypes = [c_long, c_int, c_int, c_int]
-        lib.pdf_cac_distill_workspace_floats.restype = c_long
-        lib.pdf_cac_distill_workspace_floats.argtypes = [c_int]
-        lib.pdf_spconv_supported.restype = c_int
-        lib.pdf_spconv_supported.argtypes = [c_int, c_int, c_int]
-        lib.pdf_serial_attn_supported.restype = c_int
-        lib.pdf_serial_attn_supported.argtypes = [c_int, c_int, c_int]
-        lib.pdf_serial_workspace_bytes.restype = c_long
-        lib.pdf_serial_workspace_bytes.argtypes = [c_long]
-        lib.pdf_spconv_geometry_workspace_bytes.restype = c_long
-        lib.pdf_spconv_geometry_workspace_bytes.argtypes = [c_long]
-        lib.pdf_spconv_bucket_rows.restype = c_long
-        lib.pdf_spconv_bucket_rows.argtypes = [c_long]
-        lib.pdf_spconv_wgrad_ws_floats.restype = c_long
-        lib.pdf_spconv_wgrad_ws_floats.argtypes = [c_long, c_int, c_int, c_int]
-        lib.pdf_spconv_colsum_ws_floats.restype = c_long
-        lib.pdf_spconv_colsum_ws_floats.argtypes = [c_int]
-        lib.pdf_incr_kl_workspace_floats.restype = c_long
-        lib.pdf_incr_kl_workspace_floats.argtypes = []
-        lib.pdf_incr_kl_forward.restype = c_int
-        lib.pdf_incr_kl_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, ctypes.c_float, ctypes.c_float,
-                                            c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_incr_kl_backward.restype = c_int
-        lib.pdf_incr_kl_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_lovasz_workspace_bytes.restype = c_long
-        lib.pdf_lovasz_workspace_bytes.argtypes = [c_long, c_int]
-        lib.pdf_lovasz_forward.restype = c_int
-        lib.pdf_lovasz_forward.argtypes = [c_long, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_lovasz_backward.restype = c_int
-        lib.pdf_lovasz_backward.argtypes = [c_long, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p]
-        lib.pdf_openset_metrics_workspace_bytes.restype = c_long
-        lib.pdf_openset_metrics_workspace_bytes.argtypes = [c_long, c_int]
-        lib.pdf_openset_metrics.restype = c_int
-        lib.pdf_openset_metrics.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p,
-                                            c_void_p, c_void_p]
-        lib.pdf_knn_rel_moments.restype = c_int
-        lib.pdf_knn_rel_moments.argtypes = [c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_knn_rel_moments_ws_doubles.restype = c_long
-        lib.pdf_knn_rel_moments_ws_doubles.argtypes = [c_int, c_long]
-        lib.pdf_knn_rel_moments_q.restype = c_int
-        lib.pdf_knn_rel_moments_q.argtypes = [c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        class CopySeg(ctypes.Structure):   # include/pdfops.h: PdfCopySeg
-            _fields_ = [("src", c_void_p), ("dst", c_void_p), ("nbytes", c_long), ("src_offset", c_void_p), ("sub", c_void_p),
-                        ("sub_const", c_int), ("src_elems", c_int)]
-
-        self.CopySeg = CopySeg
-        lib.pdf_stage_copy.restype = c_int
-        lib.pdf_stage_copy.argtypes = [c_int, c_void_p, c_void_p]
-        lib.pdf_scene_morton_keys.restype = c_int
-        lib.pdf_scene_morton_keys.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_sgd_chunk.restype = c_int
-        lib.pdf_sgd_chunk.argtypes = []
-        lib.pdf_sgd_step.restype = c_int
-        lib.pdf_sgd_step.argtypes = [c_int, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]
-        lib.pdf_grad_unscale.restype = c_int
-        lib.pdf_grad_unscale.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_scaler_update.restype = c_int
-        lib.pdf_scaler_update.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
-        lib.pdf_adam_step.restype = c_int
-        lib.pdf_adam_step.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                      ctypes.c_double, c_int, c_void_p, c_void_p]
-        lib.pdf_adam_grad_unscale.restype = c_int
-        lib.pdf_adam_grad_unscale.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.pdf_linbn_forward.restype = c_int
-        lib.pdf_linbn_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
-        lib.pdf_linbn_backward.restype = c_int
-        lib.pdf_linbn_backward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]
-        lib.pdf_transition_up_supported.restype = c_int
-        lib.pdf_transition_up_supported.argtypes = [c_int, c_int, c_int]
-        lib.pdf_transition_up_forward.restype = c_int
-        lib.pdf_transition_up_forward.argtypes = [c_long, c_int, c_long, c_int, c_int, c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p]
-        lib.pdf_transition_up_backward.restype = c_int
-        lib.pdf_transition_up_backward.argtypes = [c_long, c_int, c_long, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
-        lib.pdf_bn_coef_from_partial2.restype = c_int
-        lib.pdf_bn_coef_from_partial2.argtypes = [c_int, c_long, c_int, c_int, c_long, c_int, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p]
-        lib.pdf_bn_act_backward2.restype = c_int
-        lib.pdf_bn_act_backward2.argtypes = [c_long, c_int, c_long, c_int, c_void_p, c_int, c_void_p]
-        lib.pdf_rowlin_wgrad2.restype = c_int
-        lib.pdf_rowlin_wgrad2.argtypes = [c_long, c_int, c_int, c_long, c_int, c_int, c_void_p, c_int, c_void_p]
-        lib.pdf_bottleneck_forward.restype = c_int
-        lib.pdf_bottleneck_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_int, c_int, c_void_p]
-        lib.pdf_bottleneck_backward.restype = c_int
-        lib.pdf_bottleneck_backward.argtypes = [c_long, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-        for nm in ("pre_backward", "post_backward"):
-            f = getattr(lib, "pdf_block_" + nm)
-            f.restype = c_int
-            f.argtypes = [c_long, c_int, c_void_p, c_int, c_int, c_void_p]
-        lib.pdf_rowlin_multi.restype = c_int
-        lib.pdf_rowlin_multi.argtypes = [c_long, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                         c_int, c_void_p, c_long, c_int, c_int, c_void_p]
-        lib.pdf_kpconv_supported.restype = c_int
-        lib.pdf_kpconv_supported.argtypes = [c_int, c_int]
-        for nm in ("pdf_kpconv_gather", "pdf_kpconv_scatter"):
-            f = getattr(lib, nm)
-            f.restype = c_int
-            f.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p]
-        lib.pdf_rowlin_wgrad_group.restype = c_int
-        lib.pdf_rowlin_wgrad_group.argtypes = [c_long, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
-                                               c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-        lib.pdf_rowlin_wgrad_multi.restype = c_int
-        lib.pdf_rowlin_wgrad_multi.argtypes = [c_long, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int,
-                                               c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-        lib.pdf_rowlin_wgrad_ws_floats.restype = c_long
-        lib.pdf_rowlin_wgrad_ws_floats.argtypes = [c_long, c_int, c_int, c_int]
-        lib.pdf_rowlin_dgrad_bstats.restype = c_int
-        lib.pdf_rowlin_dgrad_bstats.argtypes = [c_long, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_long,
-                                                c_void_p, c_int, c_void_p, ctypes.POINTER(c_int), c_int, c_void_p]
-        lib.pdf_bn_act_backward_presummed.restype = c_int
-        lib.pdf_bn_act_backward_presummed.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
-                                                      c_void_p, c_void_p]
-        lib.pdf_rowlin_partial_floats.restype = c_long
-        lib.pdf_rowlin_partial_floats.argtypes = [c_long, c_int]
-        lib.pdf_rowlin_partial_rows.restype = c_int
-        lib.pdf_rowlin_partial_rows.argtypes = [c_long, c_int, c_int]
-        lib.pdf_rowlin_forward.restype = c_int
-        lib.pdf_rowlin_forward.argtypes = [c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p]
-        lib.pdf_rowlin_wgrad.restype = c_int
-        lib.pdf_rowlin_wgrad.argtypes = [c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int,
-                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-        lib.pdf_bn_coef_from_partial.restype = c_int
-        lib.pdf_bn_coef_from_partial.argtypes = [c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                 ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]
-        lib.pdf_bn_coef.restype = c_int
-        lib.pdf_bn_coef.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float,
-                                    ctypes.c_float, c_void_p, c_void_p, c_void_p]
-        lib.pdf_bn_apply.restype = c_int
-        lib.pdf_bn_apply.argtypes = [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-        lib.pdf_bn_supported.restype = c_int
-        lib.pdf_bn_supported.argtypes = [c_int]
-        lib.pdf_bn_partial_floats.restype = c_long
-        lib.pdf_bn_partial_floats.argtypes = [c_long, c_int]
-        lib.pdf_bn_act_forward.restype = c_int
-        lib.pdf_bn_act_forward.argtypes = [c_long, c_int] + [c_void_p] * 6 + [c_int, ctypes.c_float, ctypes.c_float, c_int] + [c_void_p] * 4
-        lib.pdf_bn_act_backward.restype = c_int
-        lib.pdf_bn_act_backward.argtypes = [c_long, c_int] + [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 5
-        lib.pdf_pt_layer_supported.restype = c_int
-        lib.pdf_pt_layer_supported.argtypes = [c_int, c_int]
-        for fn in (lib.pdf_pt_layer_partial_floats, lib.pdf_pt_layer_bwd_partial_floats):
-            fn.restype = c_long
-            fn.argtypes = [c_int, c_int, c_int]
-        lib.pdf_pt_layer_bwd_sums_floats.restype = c_long
-        lib.pdf_pt_layer_bwd_sums_floats.argtypes = [c_int]
-        lib.pdf_pt_layer_forward.restype = c_int
-        lib.pdf_pt_layer_forward.argtypes = [c_int, c_int, c_int] + [c_void_p] * 8 + [c_int, ctypes.c_float, ctypes.c_float] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p]
-        lib.pdf_knn_grid_build.restype = c_int
-        lib.pdf_knn_grid_build.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p]
-        lib.pdf_knn_query_grid.restype = c_int
-        lib.pdf_knn_query_grid.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]
-        lib.pdf_pt_layer_backward.restype = c_int
-        lib.pdf_pt_layer_backward.argtypes = [c_int, c_int, c_int] + [c_void_p] * 19 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p, c_void_p, c_void_p]
-        lib.pdf_grid_pool_workspace_bytes.restype = c_long
-        lib.pdf_grid_pool_workspace_bytes.argtypes = [c_long]
-        lib.pdf_gva_supported.restype = c_int
-        lib.pdf_gva_supported.argtypes = [c_int, c_int, c_int]
+        super().__init__(lib, "pdf_", "cuda", True, extra_protos=None)
+        self.CopySeg = _abi.PdfCopySeg
+        self.collect_fps_stats = False  # debug: keep the work counters of the last bucketed FPS call (forces a sync)
+        self.last_fps_stats = None
         self.fps_mode = os.environ.get("PDFOPS_FPS", "bucketed")  # "bucketed" | "plain"
         self.knn_mode = os.environ.get("PDFOPS_KNN", "grid")      # "grid" | "scan"
-        lib.pdf_knn_workspace_bytes.restype = c_long
-        lib.pdf_knn_workspace_bytes.argtypes = [c_int, c_int, c_int]
-        lib.pdf_graph_forest_workspace_bytes.restype = c_long
-        lib.pdf_region_grow_list_points.restype = c_long
-        lib.pdf_region_grow_list_points.argtypes = []
-        lib.pdf_graph_forest_workspace_bytes.argtypes = [c_long, c_long, c_long]
-        lib.pdf_knn_grid_supported.restype = c_int
-        lib.pdf_knn_grid_supported.argtypes = [c_int]
-        lib.pdf_knn_query_ws.restype = c_int
-        lib.pdf_knn_query_ws.argtypes = [c_int, c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_long, c_void_p]
-        lib.pdf_knn_query_ws_counted.restype = c_int
-        lib.pdf_knn_query_ws_counted.argtypes = [c_int, c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_long, c_void_p, c_void_p]
 
     KNN_GRID_MAX_SCENES = 64
     # scatter-adds of the gather family as segmented gathers over inverse tables (PDFOPS_INVERSE=0: the atomic kernels, for A/B runs)
@@ -1025,9 +661,7 @@ class HipBackend(CBackend):
         require_current_device(xyz, offset)
         nbytes = int(self.lib.pdf_knn_workspace_bytes(b, n, int(max(m_max, n))))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=xyz.device)
-        rc = self.lib.pdf_knn_grid_build(n, self._ptr(xyz), self._ptr(offset), b, self._ptr(ws), nbytes, c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_knn_grid_build failed with status {rc}")
+        self._launch("knn_grid_build", n, self._ptr(xyz), self._ptr(offset), b, self._ptr(ws), nbytes)
         return ws
 
     def knn_query(self, nsample, xyz, new_xyz, offset, new_offset, grid=None):
@@ -1039,10 +673,8 @@ class HipBackend(CBackend):
                 raise PdfOpsError("knn_query: the grid workspace was built for fewer queries")
             idx = self._new(xyz, (m, nsample), torch.int32)
             dist2 = self._new(xyz, (m, nsample), torch.float32)
-            rc = self.lib.pdf_knn_query_grid(m, int(nsample), n, self._ptr(xyz), self._ptr(new_xyz), self._ptr(offset), self._ptr(new_offset), b,
-                                             self._ptr(idx), self._ptr(dist2), self._ptr(grid), grid.numel(), c_void_p(raw_stream()))
-            if rc != 0:
-                raise PdfOpsError(f"pdf_knn_query_grid failed with status {rc}")
+            self._launch("knn_query_grid", m, int(nsample), n, self._ptr(xyz), self._ptr(new_xyz), self._ptr(offset), self._ptr(new_offset), b,
+                         self._ptr(idx), self._ptr(dist2), self._ptr(grid), grid.numel())
             return idx, dist2
         if self.knn_mode == "scan" or not self.lib.pdf_knn_grid_supported(int(nsample)):
             return super().knn_query(nsample, xyz, new_xyz, offset, new_offset)
@@ -1056,11 +688,8 @@ class HipBackend(CBackend):
         dist2 = self._new(xyz, (m, nsample), torch.float32)
         nbytes = int(self.lib.pdf_knn_workspace_bytes(b, n, m))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=xyz.device)
-        rc = self.lib.pdf_knn_query_ws(m, int(nsample), n, self._ptr(xyz), self._ptr(new_xyz), self._ptr(offset),
-                                       self._ptr(new_offset), b, self._ptr(idx), self._ptr(dist2), self._ptr(ws), nbytes,
-                                       c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_knn_query_ws failed with status {rc}")
+        self._launch("knn_query_ws", m, int(nsample), n, self._ptr(xyz), self._ptr(new_xyz), self._ptr(offset),
+                     self._ptr(new_offset), b, self._ptr(idx), self._ptr(dist2), self._ptr(ws), nbytes)
         return idx, dist2
 
     def scene_morton_keys(self, xyz, offset):
@@ -1070,9 +699,7 @@ class HipBackend(CBackend):
         n, b = xyz.shape[0], offset.shape[0]
         keys = torch.empty((n,), dtype=torch.int64, device=xyz.device)
         bounds = torch.empty((4 * b,), dtype=torch.float32, device=xyz.device)
-        rc = self.lib.pdf_scene_morton_keys(n, b, self._ptr(xyz), self._ptr(offset), self._ptr(bounds), self._ptr(keys), c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_scene_morton_keys failed with status {rc}")
+        self._launch("scene_morton_keys", n, b, self._ptr(xyz), self._ptr(offset), self._ptr(bounds), self._ptr(keys))
         return keys
 
     def knn_query_counted(self, nsample, xyz, new_xyz, offset, new_offset):
@@ -1085,11 +712,8 @@ class HipBackend(CBackend):
         nbytes = int(self.lib.pdf_knn_workspace_bytes(b, n, m))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=xyz.device)
         pairs = torch.zeros((1,), dtype=torch.int64, device=xyz.device)
-        rc = self.lib.pdf_knn_query_ws_counted(m, int(nsample), n, self._ptr(xyz), self._ptr(new_xyz), self._ptr(offset),
-                                               self._ptr(new_offset), b, self._ptr(idx), self._ptr(dist2), self._ptr(ws), nbytes,
-                                               self._ptr(pairs), c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_knn_query_ws_counted failed with status {rc}")
+        self._launch("knn_query_ws_counted", m, int(nsample), n, self._ptr(xyz), self._ptr(new_xyz), self._ptr(offset),
+                     self._ptr(new_offset), b, self._ptr(idx), self._ptr(dist2), self._ptr(ws), nbytes, self._ptr(pairs))
         return idx, dist2, int(pairs.item())
 
     def farthest_point_sampling(self, xyz, offset, new_offset, n_max, m_total):
@@ -1129,13 +753,11 @@ class HipBackend(CBackend):
         H = self._new(xq, (n, k, cs), torch.float32)
         partial = self._new(xq, (int(self.lib.pdf_pt_layer_partial_floats(n, k, c)),), torch.float32)
         out = self._new(xq, (n, c), torch.float32)
-        rc = self.lib.pdf_pt_layer_forward(
-            n, k, c, self._ptr(xq), self._ptr(xk), self._ptr(xv), self._ptr(p), self._ptr(idx),
+        self._launch(
+            "pt_layer_forward", n, k, c, self._ptr(xq), self._ptr(xk), self._ptr(xv), self._ptr(p), self._ptr(idx),
             self._ptr_array(weights), self._ptr_array(bn_params), self._ptr_array(bn_buffers), int(bool(training)),
-            ctypes.c_float(eps), ctypes.c_float(momentum), self._ptr(bn), self._ptr(saved), self._ptr(H),
-            self._ptr(partial), self._ptr(out), self.layer_flags(self.storage_bf16), self._order_ptr(idx), c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_pt_layer_forward failed with status {rc}")
+            eps, momentum, self._ptr(bn), self._ptr(saved), self._ptr(H),
+            self._ptr(partial), self._ptr(out), self.layer_flags(self.storage_bf16), self._order_ptr(idx))
         return out, bn, saved, H
 
     # visiting order of the points in the fused layer passes (PDFOPS_LAYER_ORDER=0: storage order, for A/B runs)
@@ -1160,10 +782,8 @@ class HipBackend(CBackend):
         out = torch.empty((offset.shape[0], 9), dtype=torch.float64, device=xyz.device)
         ws = torch.empty((max(int(self.lib.pdf_knn_rel_moments_ws_doubles(int(offset.shape[0]), int(q.shape[0]))), 1),), dtype=torch.float64, device=xyz.device)
         require_current_device(xyz, q, offset, idx)
-        rc = self.lib.pdf_knn_rel_moments_q(int(offset.shape[0]), int(q.shape[0]), int(nsample), xyz.data_ptr(), q.data_ptr(), offset.data_ptr(),
-                                            idx.data_ptr(), out.data_ptr(), ws.data_ptr(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_knn_rel_moments failed with status {rc}")
+        self._launch("knn_rel_moments_q", int(offset.shape[0]), int(q.shape[0]), int(nsample), xyz.data_ptr(), q.data_ptr(), offset.data_ptr(),
+                     idx.data_ptr(), out.data_ptr(), ws.data_ptr())
         return out
 
     def _order_ptr(self, idx):
@@ -1187,15 +807,13 @@ class HipBackend(CBackend):
         partial = self._new(xq, (int(self.lib.pdf_pt_layer_bwd_partial_floats(n, k, c)),), torch.float32)
         nsum = int(self.lib.pdf_pt_layer_bwd_sums_floats(c))
         sums = self._new(xq, (nsum + 2 * (3 + c + cs),), torch.float32)
-        rc = self.lib.pdf_pt_layer_backward(
-            n, k, c, self._ptr(xq), self._ptr(xk), self._ptr(xv), self._ptr(p), self._ptr(idx),
+        self._launch(
+            "pt_layer_backward", n, k, c, self._ptr(xq), self._ptr(xk), self._ptr(xv), self._ptr(p), self._ptr(idx),
             self._ptr_array(weights), self._ptr(bn), self._ptr(saved), self._ptr(H), self._ptr(gout),
             self._ptr(gxq), self._ptr(gxk), self._ptr(gxv), self._ptr(G2), self._ptr(G3), self._ptr(Wsm), self._ptr(GR),
             self._ptr(inv_off), self._ptr(inv_entry), int(entry_base), self._ptr(partial),
             self._ptr(sums), self.layer_flags(self.storage_bf16 if storage_bf16 is None else storage_bf16), self._order_ptr(idx),
-            self._moments_ptr(idx), c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_pt_layer_backward failed with status {rc}")
+            self._moments_ptr(idx))
         # unpack the parameter-gradient sections (layout: csrc/fused_layer.hip, pdf_pt_layer_backward)
         o1 = 0
         o2 = o1 + 3 * cs + cs * cs
@@ -1456,12 +1074,9 @@ class HipBackend(CBackend):
         hist = torch.empty((3, k), dtype=torch.int64, device=x.device)
         record = torch.empty((4,), dtype=torch.float64, device=x.device)
         ws = torch.empty((max(int(self.lib.pdf_openset_metrics_workspace_bytes(n, c)), 8),), dtype=torch.uint8, device=x.device)
-        rc = self.lib.pdf_openset_metrics(n, c, None if logits is None else logits.data_ptr(), None if pred is None else pred.data_ptr(),
-                                          None if score is None else score.data_ptr(), target.data_ptr(), int(ignore),
-                                          None if unknown is None else unknown.data_ptr(), int(k), hist.data_ptr(), record.data_ptr(),
-                                          ws.data_ptr(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_openset_metrics failed with status {rc}")
+        self._launch("openset_metrics", n, c, None if logits is None else logits.data_ptr(), None if pred is None else pred.data_ptr(),
+                     None if score is None else score.data_ptr(), target.data_ptr(), int(ignore),
+                     None if unknown is None else unknown.data_ptr(), int(k), hist.data_ptr(), record.data_ptr(), ws.data_ptr())
         return hist, record
 
     def rowlin(self, x, w, bias=None, coef=None, relu=False, transpose_w=False, out=None, accumulate=False, stats=False):
@@ -1473,13 +1088,11 @@ class HipBackend(CBackend):
         if stats:
             partial = torch.empty((int(self.lib.pdf_rowlin_partial_floats(n, o)),), dtype=torch.float32, device=x.device)
             partial._pdf_rows = int(self.lib.pdf_rowlin_partial_rows(n, k, o))
-        rc = self.lib.pdf_rowlin_forward(n, k, o, x.data_ptr(), x.stride(0), w.data_ptr(), int(transpose_w),
-                                         None if bias is None else bias.data_ptr(),
-                                         None if coef is None else coef.data_ptr(),
-                                         None if coef is None else coef.data_ptr() + 4 * k, int(relu), y.data_ptr(), y.stride(0),
-                                         int(accumulate), None if partial is None else partial.data_ptr(), current_mma_input(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_rowlin_forward failed with status {rc}")
+        self._launch("rowlin_forward", n, k, o, x.data_ptr(), x.stride(0), w.data_ptr(), int(transpose_w),
+                     None if bias is None else bias.data_ptr(),
+                     None if coef is None else coef.data_ptr(),
+                     None if coef is None else coef.data_ptr() + 4 * k, int(relu), y.data_ptr(), y.stride(0),
+                     int(accumulate), None if partial is None else partial.data_ptr(), current_mma_input())
         return y, partial
 
     @staticmethod
@@ -1491,12 +1104,10 @@ class HipBackend(CBackend):
         n, k = xs[0].shape
         o = ws[0].shape[1] if transpose_w else ws[0].shape[0]
         ys = [torch.empty((n, o), dtype=torch.float32, device=xs[0].device) for _ in range(nout)]
-        rc = self.lib.pdf_rowlin_multi(n, k, o, len(xs), nout, self._ptrs(xs), xs[0].stride(0), self._ptrs(ws), int(transpose_w),
-                                       None if biases is None else self._ptrs(biases),
-                                       None if coef is None else coef.data_ptr(), None if coef is None else coef.data_ptr() + 4 * k,
-                                       int(relu), self._ptrs(ys), o, 0, current_mma_input(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_rowlin_multi failed with status {rc}")
+        self._launch("rowlin_multi", n, k, o, len(xs), nout, self._ptrs(xs), xs[0].stride(0), self._ptrs(ws), int(transpose_w),
+                     None if biases is None else self._ptrs(biases),
+                     None if coef is None else coef.data_ptr(), None if coef is None else coef.data_ptr() + 4 * k,
+                     int(relu), self._ptrs(ys), o, 0, current_mma_input())
         return ys
 
     def rowlin_dgrad_bn_backward(self, gs, ws, bx, coef, training=True, relu=True):
@@ -1510,17 +1121,12 @@ class HipBackend(CBackend):
         partial = self._new(bx, (int(self.lib.pdf_rowlin_partial_floats(n, o)),), torch.float32)
         rows = c_int(0)
         sums = self._new(bx, (2 * o,), torch.float32)
-        rc = self.lib.pdf_rowlin_dgrad_bstats(n, k, o, len(gs), self._ptrs(gs), gs[0].stride(0), self._ptrs(ws), dy.data_ptr(), o,
-                                              bx.data_ptr(), bx.stride(0), coef.data_ptr(), int(bool(relu)), partial.data_ptr(),
-                                              ctypes.byref(rows), current_mma_input(), self._stream())
-        if rc == -3:   # PDF_ERR_UNSUPPORTED
+        if self._launch("rowlin_dgrad_bstats", n, k, o, len(gs), self._ptrs(gs), gs[0].stride(0), self._ptrs(ws), dy.data_ptr(), o,
+                        bx.data_ptr(), bx.stride(0), coef.data_ptr(), int(bool(relu)), partial.data_ptr(),
+                        ctypes.byref(rows), current_mma_input(), unsupported_ok=True):
             return None
-        if rc != 0:
-            raise PdfOpsError(f"pdf_rowlin_dgrad_bstats failed with status {rc}")
-        rc = self.lib.pdf_bn_act_backward_presummed(n, o, dy.data_ptr(), bx.data_ptr(), coef.data_ptr(), int(bool(training)), int(bool(relu)),
-                                                    partial.data_ptr(), rows.value, sums.data_ptr(), dy.data_ptr(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_bn_act_backward_presummed failed with status {rc}")
+        self._launch("bn_act_backward_presummed", n, o, dy.data_ptr(), bx.data_ptr(), coef.data_ptr(), int(bool(training)), int(bool(relu)),
+                     partial.data_ptr(), rows.value, sums.data_ptr(), dy.data_ptr())
         return dy, sums[o:], sums[:o]
 
     def wgrad_workspace(self, n, k, o, ng, device):
@@ -1533,11 +1139,9 @@ class HipBackend(CBackend):
         dws = [torch.empty((o, k), dtype=torch.float32, device=x.device) for _ in gs]
         dbs = [torch.empty((o,), dtype=torch.float32, device=x.device) for _ in gs]
         ws = self.wgrad_workspace(n, k, o, len(gs), x.device)
-        rc = self.lib.pdf_rowlin_wgrad_multi(n, k, o, len(gs), self._ptrs(gs), gs[0].stride(0), x.data_ptr(), x.stride(0),
-                                             None if coef is None else coef.data_ptr(), None if coef is None else coef.data_ptr() + 4 * k,
-                                             int(relu), self._ptrs(dws), self._ptrs(dbs), ws.data_ptr(), current_mma_input(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_rowlin_wgrad_multi failed with status {rc}")
+        self._launch("rowlin_wgrad_multi", n, k, o, len(gs), self._ptrs(gs), gs[0].stride(0), x.data_ptr(), x.stride(0),
+                     None if coef is None else coef.data_ptr(), None if coef is None else coef.data_ptr() + 4 * k,
+                     int(relu), self._ptrs(dws), self._ptrs(dbs), ws.data_ptr(), current_mma_input())
         return dws, dbs
 
     # -- rigid KPConv of the StratifiedTransformer stem (csrc/kpconv.hip): gather-accumulate and its adjoint
@@ -1549,20 +1153,16 @@ class HipBackend(CBackend):
         n, m = neighbors.shape
         kp, cin = k_points.shape[0], x.shape[1]
         out = torch.empty((n, kp * cin), dtype=torch.float32, device=x.device)
-        rc = self.lib.pdf_kpconv_gather(n, m, kp, cin, query.data_ptr(), support.data_ptr(), neighbors.data_ptr(), x.data_ptr(),
-                                        k_points.data_ptr(), ctypes.c_float(extent), out.data_ptr(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_kpconv_gather failed with status {rc}")
+        self._launch("kpconv_gather", n, m, kp, cin, query.data_ptr(), support.data_ptr(), neighbors.data_ptr(), x.data_ptr(),
+                     k_points.data_ptr(), extent, out.data_ptr())
         return out
 
     def kpconv_scatter(self, query, support, neighbors, grad_weighted, k_points, extent, rows, cin):
         """-> grad_x (rows, C_in): the adjoint of kpconv_gather."""
         n, m = neighbors.shape
         gx = torch.zeros((rows, cin), dtype=torch.float32, device=grad_weighted.device)
-        rc = self.lib.pdf_kpconv_scatter(n, m, k_points.shape[0], cin, query.data_ptr(), support.data_ptr(), neighbors.data_ptr(),
-                                         grad_weighted.data_ptr(), k_points.data_ptr(), ctypes.c_float(extent), gx.data_ptr(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_kpconv_scatter failed with status {rc}")
+        self._launch("kpconv_scatter", n, m, k_points.shape[0], cin, query.data_ptr(), support.data_ptr(), neighbors.data_ptr(),
+                     grad_weighted.data_ptr(), k_points.data_ptr(), extent, gx.data_ptr())
         return gx
 
     def rowlin_wgrad_group(self, gs, xs, coefs, relus, need_bias):
@@ -1578,12 +1178,9 @@ class HipBackend(CBackend):
         P = lambda ts: (c_void_p * len(ts))(*[None if t is None else (t if isinstance(t, int) else t.data_ptr()) for t in ts])
         sc = [None if cf is None else cf.data_ptr() for cf in coefs]
         sh = [None if cf is None else cf.data_ptr() + 4 * k for cf in coefs]
-        rc = self.lib.pdf_rowlin_wgrad_group(n, k, o, len(gs), P(gs), gs[0].stride(0), P(xs), xs[0].stride(0), P(sc), P(sh),
-                                             (c_int * len(gs))(*[int(bool(r)) for r in relus]), P(dws), P(dbs), ws.data_ptr(), current_mma_input(), self._stream())
-        if rc == -3:   # PDF_ERR_UNSUPPORTED
+        if self._launch("rowlin_wgrad_group", n, k, o, len(gs), P(gs), gs[0].stride(0), P(xs), xs[0].stride(0), P(sc), P(sh),
+                        (c_int * len(gs))(*[int(bool(r)) for r in relus]), P(dws), P(dbs), ws.data_ptr(), current_mma_input(), unsupported_ok=True):
             return None
-        if rc != 0:
-            raise PdfOpsError(f"pdf_rowlin_wgrad_group failed with status {rc}")
         return dws, dbs
 
     def rowlin_wgrad(self, g, x, coef, relu, need_bias):
@@ -1592,12 +1189,10 @@ class HipBackend(CBackend):
         dw = torch.empty((o, k), dtype=torch.float32, device=x.device)
         db = torch.empty((o,), dtype=torch.float32, device=x.device) if need_bias else None
         ws = self.wgrad_workspace(n, k, o, 1, x.device)
-        rc = self.lib.pdf_rowlin_wgrad(n, k, o, g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0),
-                                       None if coef is None else coef.data_ptr(),
-                                       None if coef is None else coef.data_ptr() + 4 * k, int(relu), dw.data_ptr(),
-                                       None if db is None else db.data_ptr(), ws.data_ptr(), current_mma_input(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_rowlin_wgrad failed with status {rc}")
+        self._launch("rowlin_wgrad", n, k, o, g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0),
+                     None if coef is None else coef.data_ptr(),
+                     None if coef is None else coef.data_ptr() + 4 * k, int(relu), dw.data_ptr(),
+                     None if db is None else db.data_ptr(), ws.data_ptr(), current_mma_input())
         return dw, db
 
     def bn_coef_from_partial(self, partial, n, c, bn, training):
@@ -1605,12 +1200,8 @@ class HipBackend(CBackend):
         coef = torch.empty((4 * c,), dtype=torch.float32, device=partial.device if partial is not None else bn.weight.device)
         if training:
             rows = partial._pdf_rows
-            rc = self.lib.pdf_bn_coef_from_partial(partial.data_ptr(), rows, n, c, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                                   bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ctypes.c_float(bn.eps),
-                                                   ctypes.c_float(bn.momentum),
-                                                   coef.data_ptr(), self._stream())
-            if rc != 0:
-                raise PdfOpsError(f"pdf_bn_coef_from_partial failed with status {rc}")
+            self._launch("bn_coef_from_partial", partial.data_ptr(), rows, n, c, bn.weight.data_ptr(), bn.bias.data_ptr(),
+                         bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps, bn.momentum, coef.data_ptr())
         else:
             rstd = torch.rsqrt(bn.running_var + bn.eps)
             sc = bn.weight.detach() * rstd
@@ -1622,21 +1213,15 @@ class HipBackend(CBackend):
         n, c = x.shape
         coef = torch.empty((4 * c,), dtype=torch.float32, device=x.device)
         partial = torch.empty((int(self.lib.pdf_bn_partial_floats(n, c)),), dtype=torch.float32, device=x.device) if training else None
-        rc = self.lib.pdf_bn_coef(n, c, x.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                                  bn.running_var.data_ptr(), int(bool(training)), ctypes.c_float(bn.eps),
-                                  ctypes.c_float(bn.momentum), coef.data_ptr(),
-                                  None if partial is None else partial.data_ptr(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_bn_coef failed with status {rc}")
+        self._launch("bn_coef", n, c, x.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                     bn.running_var.data_ptr(), int(bool(training)), bn.eps, bn.momentum, coef.data_ptr(),
+                     None if partial is None else partial.data_ptr())
         return coef
 
     def bn_apply(self, x, res, coef, relu):
         n, c = x.shape
         y = torch.empty_like(x)
-        rc = self.lib.pdf_bn_apply(n, c, x.data_ptr(), None if res is None else res.data_ptr(), coef.data_ptr(), int(relu),
-                                   y.data_ptr(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_bn_apply failed with status {rc}")
+        self._launch("bn_apply", n, c, x.data_ptr(), None if res is None else res.data_ptr(), coef.data_ptr(), int(relu), y.data_ptr())
         return y
 
     def td_tables(self, p_src, p_new, idx, new_offset, inverse=None):
@@ -1647,37 +1232,28 @@ class HipBackend(CBackend):
         Z = torch.zeros((n, 32), dtype=torch.float32, device=p_src.device)
         sums = torch.zeros((b, 16), dtype=torch.float32, device=p_src.device)
         off, ent, base = inverse if inverse is not None else (None, None, 0)
-        rc = self.lib.pdf_td_tables(m, b, p_src.data_ptr(), p_new.data_ptr(), idx.data_ptr(), new_offset.data_ptr(), rel4.data_ptr(), Z.data_ptr(),
-                                    sums.data_ptr(), n, None if off is None else off.data_ptr(), None if ent is None else ent.data_ptr(), int(base),
-                                    self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_td_tables failed with status {rc}")
+        self._launch("td_tables", m, b, p_src.data_ptr(), p_new.data_ptr(), idx.data_ptr(), new_offset.data_ptr(), rel4.data_ptr(), Z.data_ptr(),
+                     sums.data_ptr(), n, None if off is None else off.data_ptr(), None if ent is None else ent.data_ptr(), int(base))
         return rel4, Z, sums
 
     # -- whole Bottleneck as one host call per direction (csrc/block.hip); thin methods so that bench.py can time them
     def bottleneck_forward(self, n, k, c, ptrs, training, eps, momentum, storage_bf16=0):
-        rc = self.lib.pdf_bottleneck_forward(n, k, c, (c_void_p * len(ptrs))(*ptrs), int(training), ctypes.c_float(eps),
-                                             ctypes.c_float(momentum), self.layer_flags(storage_bf16), current_mma_input(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_bottleneck_forward failed with status {rc}")
+        self._launch("bottleneck_forward", n, k, c, (c_void_p * len(ptrs))(*ptrs), int(training), eps, momentum,
+                     self.layer_flags(storage_bf16), current_mma_input())
 
     def bottleneck_backward(self, n, k, c, ptrs, training, entry_base=0, storage_bf16=0):
-        rc = self.lib.pdf_bottleneck_backward(n, k, c, (c_void_p * len(ptrs))(*ptrs), int(training), int(entry_base), self.layer_flags(storage_bf16), current_mma_input(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_bottleneck_backward failed with status {rc}")
+        self._launch("bottleneck_backward", n, k, c, (c_void_p * len(ptrs))(*ptrs), int(training), int(entry_base),
+                     self.layer_flags(storage_bf16), current_mma_input())
 
     # -- Bottleneck halves as single host calls (csrc/block.hip) -------------------------------------------
     def _ptable(self, tensors):
         return (c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
     def block_call(self, name, n, c, tensors, training, eps=None, momentum=None):
-        fn = getattr(self.lib, "pdf_block_" + name)
         if eps is None:
-            rc = fn(n, c, self._ptable(tensors), int(bool(training)), current_mma_input(), self._stream())
+            self._launch("block_" + name, n, c, self._ptable(tensors), int(bool(training)), current_mma_input())
         else:
-            rc = fn(n, c, self._ptable(tensors), int(bool(training)), ctypes.c_float(eps), ctypes.c_float(momentum), current_mma_input(), self._stream())
-        if rc != 0:
-            raise PdfOpsError(f"pdf_block_{name} failed with status {rc}")
+            self._launch("block_" + name, n, c, self._ptable(tensors), int(bool(training)), eps, momentum, current_mma_input())
 
     # -- BatchNorm + residual + ReLU over (n, c) rows ------------------------------------------------------
     def bn_supported(self, c):
@@ -1690,11 +1266,8 @@ class HipBackend(CBackend):
         partial = self._new(x, (int(self.lib.pdf_bn_partial_floats(n, c)),), torch.float32)
         y = self._new(x, (n, c), torch.float32)
         P = lambda t: None if t is None else self._ptr(t)
-        rc = self.lib.pdf_bn_act_forward(n, c, P(x), P(res), P(gamma), P(beta), P(running_mean), P(running_var),
-                                         int(bool(training)), ctypes.c_float(eps), ctypes.c_float(momentum), int(bool(relu)),
-                                         P(coef), P(partial), P(y), c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_bn_act_forward failed with status {rc}")
+        self._launch("bn_act_forward", n, c, P(x), P(res), P(gamma), P(beta), P(running_mean), P(running_var),
+                     int(bool(training)), eps, momentum, int(bool(relu)), P(coef), P(partial), P(y))
         return y, coef
 
     def bn_act_backward(self, gy, x, res, coef, training, relu, need_res):
@@ -1705,10 +1278,8 @@ class HipBackend(CBackend):
         gx = self._new(x, (n, c), torch.float32)
         gres = self._new(x, (n, c), torch.float32) if need_res else None
         P = lambda t: None if t is None else self._ptr(t)
-        rc = self.lib.pdf_bn_act_backward(n, c, P(gy), P(x), P(res), P(coef), int(bool(training)), int(bool(relu)), P(partial),
-                                          P(sums), P(gx), P(gres), c_void_p(raw_stream()))
-        if rc != 0:
-            raise PdfOpsError(f"pdf_bn_act_backward failed with status {rc}")
+        self._launch("bn_act_backward", n, c, P(gy), P(x), P(res), P(coef), int(bool(training)), int(bool(relu)), P(partial),
+                     P(sums), P(gx), P(gres))
         return gx, gres, sums[c:], sums[:c]  # gx, gres, d gamma, d beta
 
     def radius_neighbors_self(self, nsample, radius, xyz, offset):

@@ -6,7 +6,6 @@ single 32x32 macro-tile with K = N on ONE workgroup (measured 270 us per call, 4
 keeps nn.Linear's parameters but routes that one product through a batched GEMM over row chunks (split-K expressed
 as a batch: S = N / 2048 independent products, summed afterwards), which fills the chip.
 """
-import ctypes
 import os
 from ctypes import c_void_p
 
@@ -402,10 +401,8 @@ class _LayerNormFn(torch.autograd.Function):
         n, c = x.shape
         y = torch.empty_like(x)
         stat = torch.empty((2, n), dtype=torch.float32, device=x.device)
-        rc = be.lib.pdf_layernorm_forward(n, c, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), ctypes.c_float(eps), y.data_ptr(),
-                                          stat[0].data_ptr(), stat[1].data_ptr(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_layernorm_forward failed with status {rc}")
+        be._launch("layernorm_forward", n, c, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), eps, y.data_ptr(),
+                   stat[0].data_ptr(), stat[1].data_ptr())
         ctx.save_for_backward(x, stat, weight)
         return y
 
@@ -419,10 +416,8 @@ class _LayerNormFn(torch.autograd.Function):
         gx = torch.empty_like(x)
         gwb = torch.empty((2, c), dtype=torch.float32, device=x.device)
         partial = torch.empty((max(int(be.lib.pdf_layernorm_partial_floats(n, c)), 1),), dtype=torch.float32, device=x.device)
-        rc = be.lib.pdf_layernorm_backward(n, c, gy.data_ptr(), x.data_ptr(), stat[0].data_ptr(), stat[1].data_ptr(), weight.data_ptr(),
-                                           gx.data_ptr(), partial.data_ptr(), gwb[0].data_ptr(), gwb[1].data_ptr(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_layernorm_backward failed with status {rc}")
+        be._launch("layernorm_backward", n, c, gy.data_ptr(), x.data_ptr(), stat[0].data_ptr(), stat[1].data_ptr(), weight.data_ptr(),
+                   gx.data_ptr(), partial.data_ptr(), gwb[0].data_ptr(), gwb[1].data_ptr())
         return gx, gwb[0], gwb[1], None
 
 
@@ -706,10 +701,7 @@ class _TransitionDownFn(torch.autograd.Function):
         ws = e(int(lib.pdf_td_fwd_scratch_floats(n, cin)))
         ptrs = [x.data_ptr(), idx.data_ptr(), rel4.data_ptr(), Z.data_ptr(), consts.data_ptr(), W.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                 bn.running_mean.data_ptr(), bn.running_var.data_ptr(), coef.data_ptr(), out.data_ptr(), arg.data_ptr(), gram.data_ptr(), ws.data_ptr()]
-        rc = lib.pdf_td_forward(n, m, cin, cout, (c_void_p * len(ptrs))(*ptrs), int(training), ctypes.c_float(bn.eps),
-                                ctypes.c_float(bn.momentum), _mma(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_td_forward failed with status {rc}")
+        be._launch("td_forward", n, m, cin, cout, (c_void_p * len(ptrs))(*ptrs), int(training), bn.eps, bn.momentum, _mma())
         ctx.save_for_backward(x, idx, rel4, Z, consts, W, gamma, beta, coef, out, arg, gram)
         ctx.training = training
         return out
@@ -733,9 +725,7 @@ class _TransitionDownFn(torch.autograd.Function):
         ptrs = [gout.data_ptr(), out.data_ptr(), arg.data_ptr(), x.data_ptr(), idx.data_ptr(), rel4.data_ptr(), Z.data_ptr(), consts.data_ptr(),
                 W.data_ptr(), gamma.data_ptr(), beta.data_ptr(), coef.data_ptr(), gram.data_ptr(), gx.data_ptr(), dW.data_ptr(), dgb.data_ptr(),
                 scratch.data_ptr(), inv_off.data_ptr(), inv_entry.data_ptr()]
-        rc = lib.pdf_td_backward(n, m, cin, cout, (c_void_p * len(ptrs))(*ptrs), int(entry_base), _mma(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_td_backward failed with status {rc}")
+        be._launch("td_backward", n, m, cin, cout, (c_void_p * len(ptrs))(*ptrs), int(entry_base), _mma())
         return None, None, None, None, None, gx, dW, dgb[cout:], dgb[:cout]
 
 
@@ -776,10 +766,7 @@ class _LinBnFn(torch.autograd.Function):
         partial = e(int(lib.pdf_rowlin_partial_floats(n, o)))
         ptrs = [x.data_ptr(), W.data_ptr(), b.data_ptr() if b is not None else None, gamma.data_ptr(), beta.data_ptr(),
                 bn.running_mean.data_ptr(), bn.running_var.data_ptr(), z.data_ptr(), coef.data_ptr(), y.data_ptr(), partial.data_ptr()]
-        rc = lib.pdf_linbn_forward(n, k, o, (c_void_p * len(ptrs))(*ptrs), int(training), int(relu), ctypes.c_float(bn.eps),
-                                   ctypes.c_float(bn.momentum), _mma(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_linbn_forward failed with status {rc}")
+        be._launch("linbn_forward", n, k, o, (c_void_p * len(ptrs))(*ptrs), int(training), int(relu), bn.eps, bn.momentum, _mma())
         ctx.save_for_backward(x, z, coef, W)
         ctx.cfg = (training, relu, b is not None)
         return y
@@ -802,9 +789,7 @@ class _LinBnFn(torch.autograd.Function):
         ws = be.wgrad_workspace(n, k, o, 1, x.device)
         ptrs = [gy.data_ptr(), x.data_ptr(), z.data_ptr(), coef.data_ptr(), W.data_ptr(), gx.data_ptr() if need_gx else None, grads.data_ptr(),
                 gz.data_ptr(), partial.data_ptr(), ws.data_ptr()]
-        rc = lib.pdf_linbn_backward(n, k, o, (c_void_p * len(ptrs))(*ptrs), int(training), int(relu), _mma(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_linbn_backward failed with status {rc}")
+        be._launch("linbn_backward", n, k, o, (c_void_p * len(ptrs))(*ptrs), int(training), int(relu), _mma())
         ok = o * k
         return (None, None, None, gx, grads[:ok].view(o, k), grads[ok:ok + o] if has_bias else None, grads[ok + 2 * o:ok + 3 * o], grads[ok + o:ok + 2 * o])
 
@@ -856,10 +841,7 @@ class _TransitionUpFn(torch.autograd.Function):
         ptrs = [P(x1), P(W1), P(b1), P(g1), P(be1), P(bn1.running_mean), P(bn1.running_var),
                 P(x2), P(W2), P(b2), P(g2), P(be2), P(bn2.running_mean), P(bn2.running_var),
                 P(idx), P(weight), P(order), P(z1), P(coef1), P(part1), P(z2), P(coef2), P(part2), P(out)]
-        rc = lib.pdf_transition_up_forward(n1, k1, n2, k2, o, (c_void_p * len(ptrs))(*ptrs), 1, ctypes.c_float(bn1.eps), ctypes.c_float(bn1.momentum),
-                                           _mma(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_transition_up_forward failed with status {rc}")
+        be._launch("transition_up_forward", n1, k1, n2, k2, o, (c_void_p * len(ptrs))(*ptrs), 1, bn1.eps, bn1.momentum, _mma())
         ctx.save_for_backward(x1, z1, coef1, W1, x2, z2, coef2, W2, idx, weight)
         ctx.has_bias = (b1 is not None, b2 is not None)
         return out
@@ -887,9 +869,7 @@ class _TransitionUpFn(torch.autograd.Function):
         P = lambda t: None if t is None else t.data_ptr()
         ptrs = [P(g), P(x1), P(z1), P(coef1), P(W1), P(x2), P(z2), P(coef2), P(W2), P(weight), P(inv_off), P(inv_entry), P(src_order),
                 P(gx1), P(gx2), P(grads1), P(grads2), P(g2), P(gz1), P(gz2), P(part1), P(part2), P(ws1), P(ws2)]
-        rc = lib.pdf_transition_up_backward(n1, k1, n2, k2, o, (c_void_p * len(ptrs))(*ptrs), int(entry_base), _mma(), be._stream())
-        if rc != 0:
-            raise RuntimeError(f"pdf_transition_up_backward failed with status {rc}")
+        be._launch("transition_up_backward", n1, k1, n2, k2, o, (c_void_p * len(ptrs))(*ptrs), int(entry_base), _mma())
 
         def split(grads, k, has_bias):   # buffer: dW | db | dbeta | dgamma -> dW, db, dgamma, dbeta
             ok = o * k

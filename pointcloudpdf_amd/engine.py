@@ -1030,8 +1030,6 @@ class FusedSGD(FusedOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        from . import _native
-
         prepared = self._take_prepared()
         for gi, group in enumerate(self.param_groups):
             if group.get("dampening", 0) != 0 or group.get("nesterov", False) or group.get("maximize", False):
@@ -1040,13 +1038,10 @@ class FusedSGD(FusedOptimizer):
             if t is None:
                 continue
             nchunks, tab, chunks, ev, _alive = t
-            rc = self.be.lib.pdf_sgd_step(nchunks, tab.data_ptr(), chunks.data_ptr(), float(group["lr"]), float(group["momentum"]),
-                                          float(group["weight_decay"]), None if found_inf is None else found_inf.data_ptr(),
-                                          self.ctypes.c_void_p(_native.raw_stream()))
+            self.be._launch("sgd_step", nchunks, tab.data_ptr(), chunks.data_ptr(), float(group["lr"]), float(group["momentum"]),
+                            float(group["weight_decay"]), None if found_inf is None else found_inf.data_ptr())
             if ev is not None:
                 ev.record()
-            if rc != 0:
-                raise RuntimeError(f"pdf_sgd_step failed with status {rc}")
         return loss
 
 
@@ -1099,9 +1094,6 @@ class DeviceGradScaler:
         if not isinstance(optimizer, FusedOptimizer):
             raise TypeError("DeviceGradScaler drives engine.FusedSGD (the guarded update is part of its kernel); use torch.amp.GradScaler "
                             "with other optimizers")
-        from . import _native
-        import ctypes
-
         prepared = []
         for gi, group in enumerate(optimizer.param_groups):
             t = optimizer._tables(gi, group)
@@ -1109,11 +1101,9 @@ class DeviceGradScaler:
             if t is None:
                 continue
             nchunks, tab, chunks, _ev, _alive = t
-            unscale = getattr(optimizer.be.lib, optimizer.UNSCALE)   # (the entry that reads this optimizer's record layout)
-            rc = unscale(nchunks, tab.data_ptr(), chunks.data_ptr(), self._f[1:2].data_ptr(), self._f[2:3].data_ptr(),
-                         ctypes.c_void_p(_native.raw_stream()))
-            if rc != 0:
-                raise RuntimeError(f"{optimizer.UNSCALE} failed with status {rc}")
+            # (UNSCALE: the entry that reads this optimizer's record layout)
+            optimizer.be._launch(optimizer.UNSCALE[len("pdf_"):], nchunks, tab.data_ptr(), chunks.data_ptr(), self._f[1:2].data_ptr(),
+                                 self._f[2:3].data_ptr())
         optimizer._prepared = (optimizer._grad_key(), prepared)   # the step of this iteration reuses the tables (same gradients, same pointers)
         self._unscaled, self._prepared_for = True, optimizer
 
@@ -1128,14 +1118,9 @@ class DeviceGradScaler:
         if not self.enabled:
             return
         from . import _native
-        import ctypes
 
-        lib = _native.hip_backend().lib
-        rc = lib.pdf_scaler_update(self._f[0:1].data_ptr(), self._f[1:2].data_ptr(), self._tracker.data_ptr(), self._f[2:3].data_ptr(),
-                                   ctypes.c_float(self.growth_factor), ctypes.c_float(self.backoff_factor), int(self.growth_interval),
-                                   ctypes.c_void_p(_native.raw_stream()))
-        if rc != 0:
-            raise RuntimeError(f"pdf_scaler_update failed with status {rc}")
+        _native.hip_backend()._launch("scaler_update", self._f[0:1].data_ptr(), self._f[1:2].data_ptr(), self._tracker.data_ptr(),
+                                      self._f[2:3].data_ptr(), self.growth_factor, self.backoff_factor, int(self.growth_interval))
         self._unscaled = False
         opt, self._prepared_for = getattr(self, "_prepared_for", None), None
         if opt is not None:   # (an iteration that skipped optimizer.step(): its tables die with it)

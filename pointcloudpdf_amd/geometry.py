@@ -607,8 +607,6 @@ class StaticGeometry(Geometry):
         launch on the current stream (csrc/stage_copy.hip), reading ``geom``'s tensors where they lie.  ``extra``: further
         (source, destination) tensor pairs to move in the same launch (the batch's own tensors).  Nothing is allocated; the version
         counters of the static views do not move."""
-        import ctypes
-
         be = _native.hip_backend()
         src = geom.flat_sources()
         if len(src) != len(self.layout.items):
@@ -634,9 +632,7 @@ class StaticGeometry(Geometry):
             sg.src, sg.dst, sg.nbytes = a.data_ptr(), b.data_ptr(), a.numel() * a.element_size()
             sg.src_offset, sg.sub, sg.sub_const, sg.src_elems = None, None, 0, 0
         _native.require_current_device(self.flat)
-        rc = be.lib.pdf_stage_copy(n, segs, ctypes.c_void_p(_native.raw_stream()))
-        if rc != 0:
-            raise _native.PdfOpsError(f"pdf_stage_copy failed with status {rc}")
+        be._launch("stage_copy", n, segs)
         return self
 
 

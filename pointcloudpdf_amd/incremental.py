@@ -33,7 +33,6 @@ class _FusedIncrKl(torch.autograd.Function):
     @staticmethod
     @_amp_fwd
     def forward(ctx, pred, teacher, labels, ignore, inv_tp, inv_tt):
-        import ctypes
         from . import _native
 
         be = _native.hip_backend()
@@ -43,18 +42,14 @@ class _FusedIncrKl(torch.autograd.Function):
         # [sum, 1 / (T_p N), loss, -] + the per-workgroup partial sums (added in a fixed order: csrc/incr_distill.hip)
         acc = torch.empty((int(be.lib.pdf_incr_kl_workspace_floats()),), dtype=torch.float32, device=pred.device)
         _native.require_current_device(pred, teacher, labels)
-        s = ctypes.c_void_p(_native.raw_stream())
-        rc = be.lib.pdf_incr_kl_forward(n, cs, ct, pred.data_ptr(), teacher.data_ptr(), labels.data_ptr(), ignore, inv_tp, inv_tt,
-                                        grad.data_ptr(), acc.data_ptr(), acc.data_ptr() + 8, s)
-        if rc != 0:
-            raise RuntimeError(f"pdf_incr_kl_forward failed with status {rc}")
+        be._launch("incr_kl_forward", n, cs, ct, pred.data_ptr(), teacher.data_ptr(), labels.data_ptr(), ignore, inv_tp, inv_tt,
+                   grad.data_ptr(), acc.data_ptr(), acc.data_ptr() + 8)
         ctx.save_for_backward(grad, acc)
         return acc[2]
 
     @staticmethod
     @_amp_bwd
     def backward(ctx, gy):
-        import ctypes
         from . import _native
 
         dgrad, acc = ctx.saved_tensors
@@ -62,10 +57,7 @@ class _FusedIncrKl(torch.autograd.Function):
         gy = gy.contiguous().float()
         out = torch.empty_like(dgrad)   # the saved buffer stays untouched: the node may be differentiated again (retain_graph)
         _native.require_current_device(dgrad, gy)
-        s = ctypes.c_void_p(_native.raw_stream())
-        rc = _native.hip_backend().lib.pdf_incr_kl_backward(n, cs, dgrad.data_ptr(), acc.data_ptr(), gy.data_ptr(), out.data_ptr(), s)
-        if rc != 0:
-            raise RuntimeError(f"pdf_incr_kl_backward failed with status {rc}")
+        _native.hip_backend()._launch("incr_kl_backward", n, cs, dgrad.data_ptr(), acc.data_ptr(), gy.data_ptr(), out.data_ptr())
         return out, None, None, None, None, None
 
 

@@ -105,7 +105,6 @@ class _FusedLovasz(torch.autograd.Function):
     @staticmethod
     @_amp_fwd
     def forward(ctx, pred, target, ignore, class_mask):
-        import ctypes
         from . import _native
 
         be = _native.hip_backend()
@@ -116,19 +115,15 @@ class _FusedLovasz(torch.autograd.Function):
         # every byte is written before it is read (csrc/lovasz.hip): nothing to zero, no memset node in a captured step
         ws = torch.empty((int(be.lib.pdf_lovasz_workspace_bytes(n, c)),), dtype=torch.uint8, device=pred.device)
         _native.require_current_device(pred, target)
-        s = ctypes.c_void_p(_native.raw_stream())
-        rc = be.lib.pdf_lovasz_forward(n, c, pred.data_ptr(), target.data_ptr(), ignore,
-                                       class_mask.data_ptr() if class_mask is not None else None, prob.data_ptr(), dlogits.data_ptr(),
-                                       out.data_ptr(), ws.data_ptr(), s)
-        if rc != 0:
-            raise RuntimeError(f"pdf_lovasz_forward failed with status {rc}")
+        be._launch("lovasz_forward", n, c, pred.data_ptr(), target.data_ptr(), ignore,
+                   class_mask.data_ptr() if class_mask is not None else None, prob.data_ptr(), dlogits.data_ptr(),
+                   out.data_ptr(), ws.data_ptr())
         ctx.save_for_backward(dlogits)
         return out[0]
 
     @staticmethod
     @_amp_bwd
     def backward(ctx, gy):
-        import ctypes
         from . import _native
 
         (dlogits,) = ctx.saved_tensors
@@ -136,10 +131,7 @@ class _FusedLovasz(torch.autograd.Function):
         gy = gy.contiguous().float()
         out = torch.empty_like(dlogits)   # the saved buffer stays untouched: the node may be differentiated again (retain_graph)
         _native.require_current_device(dlogits, gy)
-        s = ctypes.c_void_p(_native.raw_stream())
-        rc = _native.hip_backend().lib.pdf_lovasz_backward(n, c, dlogits.data_ptr(), gy.data_ptr(), 1.0, out.data_ptr(), s)
-        if rc != 0:
-            raise RuntimeError(f"pdf_lovasz_backward failed with status {rc}")
+        _native.hip_backend()._launch("lovasz_backward", n, c, dlogits.data_ptr(), gy.data_ptr(), 1.0, out.data_ptr())
         return out, None, None, None
 
 

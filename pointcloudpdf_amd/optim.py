@@ -23,11 +23,9 @@ class FusedOptimizer(torch.optim.Optimizer):
     UNSCALE = "pdf_grad_unscale"
 
     def __init__(self, params, defaults, backend=None):
-        import ctypes
         from . import _native
 
         self.be = backend if backend is not None else _native.hip_backend()   # (backend: tests of the host logic without a GPU)
-        self.ctypes = ctypes
         self._rows = 0
         self._ring, self._tabs, self._spare, self._captured, self._plans, self._n = [], [], [], [], {}, 0
         super().__init__(params, defaults)
@@ -234,8 +232,6 @@ class FusedAdamW(FusedOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        from . import _native
-
         name = type(self).__name__
         prepared = self._take_prepared()
         for gi, group in enumerate(self.param_groups):
@@ -248,15 +244,12 @@ class FusedAdamW(FusedOptimizer):
             nchunks, tab, chunks, ev, grads = t
             beta1, beta2 = group["betas"]
             # (one record per gradient: a ring table has the largest group's rows, and only the first len(grads) are written)
-            rc = self.be.lib.pdf_adam_step(nchunks, len(grads), tab.data_ptr(), chunks.data_ptr(), float(group["lr"]), float(beta1),
-                                           float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                                           1 if group.get("decoupled_weight_decay", self.DECOUPLED) else 0,
-                                           None if found_inf is None else found_inf.data_ptr(), self.ctypes.c_void_p(_native.raw_stream()))
+            self.be._launch("adam_step", nchunks, len(grads), tab.data_ptr(), chunks.data_ptr(), float(group["lr"]), float(beta1),
+                            float(beta2), float(group["eps"]), float(group["weight_decay"]),
+                            1 if group.get("decoupled_weight_decay", self.DECOUPLED) else 0,
+                            None if found_inf is None else found_inf.data_ptr())
             if ev is not None:
                 ev.record()
-            if rc != 0:
-                raise RuntimeError(f"pdf_adam_step failed with status {rc} (lr {group['lr']}, betas {group['betas']}, eps {group['eps']}, "
-                                   f"weight_decay {group['weight_decay']})")
         return loss
 
 

@@ -85,7 +85,6 @@ class _FusedCE(torch.autograd.Function):
     @staticmethod
     @_amp_fwd
     def forward(ctx, pred, target, ignore):
-        import ctypes
         from . import _native
 
         be = _native.hip_backend()
@@ -94,17 +93,13 @@ class _FusedCE(torch.autograd.Function):
         # [sum, count, mean, -] + the per-workgroup partial sums (added in a fixed order: csrc/loss.hip)
         acc = torch.empty((int(be.lib.pdf_ce_workspace_floats()),), dtype=torch.float32, device=pred.device)
         _native.require_current_device(pred, target)
-        s = ctypes.c_void_p(_native.raw_stream())
-        rc = be.lib.pdf_ce_forward(n, c, pred.data_ptr(), target.data_ptr(), ignore, grad.data_ptr(), acc.data_ptr(), acc.data_ptr() + 8, s)
-        if rc != 0:
-            raise RuntimeError(f"pdf_ce_forward failed with status {rc}")
+        be._launch("ce_forward", n, c, pred.data_ptr(), target.data_ptr(), ignore, grad.data_ptr(), acc.data_ptr(), acc.data_ptr() + 8)
         ctx.save_for_backward(grad, acc)
         return acc[2]
 
     @staticmethod
     @_amp_bwd
     def backward(ctx, gy):
-        import ctypes
         from . import _native
 
         dlogits, acc = ctx.saved_tensors
@@ -112,10 +107,7 @@ class _FusedCE(torch.autograd.Function):
         gy = gy.contiguous().float()
         out = torch.empty_like(dlogits)   # the saved buffer stays untouched: the node may be differentiated again (retain_graph)
         _native.require_current_device(dlogits, gy)
-        s = ctypes.c_void_p(_native.raw_stream())
-        rc = _native.hip_backend().lib.pdf_ce_backward(n, c, dlogits.data_ptr(), acc.data_ptr(), gy.data_ptr(), out.data_ptr(), s)
-        if rc != 0:
-            raise RuntimeError(f"pdf_ce_backward failed with status {rc}")
+        _native.hip_backend()._launch("ce_backward", n, c, dlogits.data_ptr(), acc.data_ptr(), gy.data_ptr(), out.data_ptr())
         return out, None, None
 
 

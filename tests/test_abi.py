@@ -63,12 +63,90 @@ def test_argument_validation_needs_no_gpu(lib):
     assert rc == -2
 
 
-def test_binding_table_matches_header(lib):
+PARAM_KINDS = {"int": "i", "unsigned": "i", "unsigned int": "i", "long": "l", "long long": "l", "float": "f", "double": "d"}
+RETURN_KINDS = {"int": "si", "long": "l", "const char *": "z"}
+
+
+def declared_prototypes():
+    """{name: (return type, kinds)} of every ``RET pdf_name(PARAMS);`` in include/pdfops.h; a parameter type outside PARAM_KINDS fails."""
+    text = open(os.path.join(ROOT, "include", "pdfops.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(pdf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        kinds = ""
+        for p in [] if params.strip() in ("", "void") else params.split(","):
+            if "*" in p or "[" in p:
+                kinds += "p"
+                continue
+            ty = " ".join(w for w in p.split()[:-1] if w != "const")   # (the last word is the parameter's name)
+            assert ty in PARAM_KINDS, f"{name}: parameter {p.strip()!r} has a type this test does not know"
+            kinds += PARAM_KINDS[ty]
+        assert name not in protos, f"{name} is declared twice"
+        protos[name] = (" ".join(ret.replace("*", " * ").split()), kinds)
+    return protos
+
+
+def test_binding_table_equals_the_header():
+    """pointcloudpdf_amd/_abi.py is the header, row for row: the same names, every parameter list, a compatible return kind."""
+    from pointcloudpdf_amd import _abi
+
+    declared = declared_prototypes()
+    assert set(declared) == set(declared_symbols())   # (every name that is followed by a parenthesis parsed as a whole prototype)
+    assert set(declared) == set(_abi.ENTRIES), sorted(set(declared) ^ set(_abi.ENTRIES))
+    assert len(_abi.ENTRIES) == len(declared) > 200
+    for name, (ret, kinds) in declared.items():
+        row_ret, row_kinds = _abi.ENTRIES[name]
+        assert row_kinds == kinds, f"{name}: the table has {row_kinds!r}, the header {kinds!r}"
+        assert ret in RETURN_KINDS, f"{name}: return type {ret!r}"
+        assert row_ret in RETURN_KINDS[ret], f"{name}: the table returns {row_ret!r}, the header {ret!r}"
+    assert set(_abi.REFERENCE_OPS) <= {n[len("pdf_"):] for n, (ret, _) in _abi.ENTRIES.items() if ret == "s"}
+
+
+def test_bind_sets_every_prototype(lib):
+    from pointcloudpdf_amd import _abi, _native
+
+    be = _native.HipBackend(lib)   # binds every row (no GPU call)
+    ctype = {"i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "d": ctypes.c_double, "p": ctypes.c_void_p}
+    restype = {"s": ctypes.c_int, "i": ctypes.c_int, "l": ctypes.c_long, "z": ctypes.c_char_p}
+    for name, (ret, kinds) in _abi.ENTRIES.items():
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == len(kinds) and list(fn.argtypes) == [ctype[k] for k in kinds], name
+        assert fn.restype is restype[ret], name
+        assert fn.errcheck is None, name   # tests and tools call lib.pdf_x directly and assert on the raw status
+    assert len(lib.pdf_region_tree.argtypes) == 14
+    assert set(be._fn) == {n[len("pdf_"):] for n, (ret, _) in _abi.ENTRIES.items() if ret == "s"}
+    assert be._fn["knn_query"] is lib.pdf_knn_query   # the launch path calls the library's own function objects
+
+
+def test_launch_raises_on_a_status(lib, monkeypatch):
+    """The one launch path turns a non-zero status into PdfOpsError; the raw function still returns it (argument validation returns
+    before any launch, so this needs no device)."""
     from pointcloudpdf_amd import _native
 
-    bound = {"pdf_" + k for k in list(_native._PROTOS) + list(_native._HIP_ONLY_PROTOS)}
-    assert bound <= set(declared_symbols())
-    _native.HipBackend(lib)  # binds every prototype (no GPU call)
+    monkeypatch.setattr(_native, "raw_stream", lambda: 0)
+    be = _native.HipBackend(lib)
+    buf = (ctypes.c_float * 16)()
+    ibuf = (ctypes.c_int * 16)()
+    with pytest.raises(_native.PdfOpsError, match="pdf_knn_query failed with status -2"):
+        be._launch("knn_query", 4, 200, buf, buf, ibuf, ibuf, 1, ibuf, buf)
+    assert be.lib.pdf_knn_query(4, 200, buf, buf, ibuf, ibuf, 1, ibuf, buf, None) == -2
+    assert issubclass(_native.PdfOpsError, RuntimeError)
+
+
+def test_prototypes_live_in_one_module():
+    """No module of the package but _abi.py sets a prototype: a plain-text scan, so that the hand-written style cannot grow back."""
+    import glob
+
+    pkg = os.path.join(ROOT, "pointcloudpdf_amd")
+    files = glob.glob(os.path.join(pkg, "*.py")) + glob.glob(os.path.join(pkg, "*", "*.py"))
+    assert len(files) > 20 and os.path.join(pkg, "_abi.py") in files
+    for path in files:
+        if os.path.basename(path) == "_abi.py":
+            continue
+        text = open(path).read()
+        for needle in (".argtypes =", ".argtypes=", ".restype =", ".restype="):
+            assert needle not in text, f"{os.path.relpath(path, ROOT)} sets a prototype ({needle!r}): add a row to pointcloudpdf_amd/_abi.py instead"
 
 
 def test_code_object_targets_gfx950():
@@ -94,12 +172,12 @@ def test_mma_input_is_a_per_call_argument(lib):
     """ABI 4: the product-input mode is an argument of every entry that runs the streaming Linear products; the library exports no
     setter and keeps no state.  Argument validation needs no GPU: an unknown mode is PDF_ERR_BAD_ARG before anything is launched."""
     assert not hasattr(lib, "pdf_set_mma_input") and not hasattr(lib, "pdf_get_mma_input") and not hasattr(lib, "pdf_tickets_bind")
-    f = lib.pdf_rowlin_forward
-    f.restype = ctypes.c_int
-    L, I, P = ctypes.c_long, ctypes.c_int, ctypes.c_void_p
-    f.argtypes = [L, I, I, P, L, P, I, P, P, P, I, P, L, I, P, I, P]
+    from pointcloudpdf_amd import _abi
+
+    f = _abi.bind(lib, ("rowlin_forward",))["rowlin_forward"]
+    assert len(f.argtypes) == 17
     buf = (ctypes.c_float * 64)()
-    ptr = ctypes.cast(buf, P)
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
     for bad in (3, -1):
         assert f(4, 4, 4, ptr, 4, ptr, 0, None, None, None, 0, ptr, 4, 0, None, bad, None) == -1
 
