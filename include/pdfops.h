@@ -56,8 +56,9 @@ extern "C" {
  * 17 = pdf_serial_* added (no existing parameter list changed);
  * 18 = pdf_pg_* and PDF_ERR_NOT_CONVERGED added (no existing parameter list changed);
  * 19 = pdf_transition_up_* and the two-problem entries pdf_bn_coef_from_partial2 / pdf_bn_act_backward2 / pdf_rowlin_wgrad2 added (no
- *      existing parameter list changed). */
-#define PDF_ABI_VERSION 19
+ *      existing parameter list changed);
+ * 20 = pdf_rowlin_forward_stats2 / pdf_rowlin_dgrad2 / pdf_rowlin_wgrad2_paired added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 20
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -334,7 +335,7 @@ int pdf_bottleneck_backward(long n, int nsample, int c, void *const *p, int trai
 int pdf_linbn_forward(long n, int k, int o, void *const *p, int training, int relu, float eps, float momentum, int mma_input, void *stream);
 int pdf_linbn_backward(long n, int k, int o, void *const *p, int training, int relu, int mma_input, void *stream);
 /* The two-input TransitionUp, relu(bn1(x1 W1^T + b1)) + interpolation(relu(bn2(x2 W2^T + b2))) over (n1, 3) tables, as one call per direction:
- * 4 launches forward, 9 backward; train mode only; the same bits as two pdf_linbn_* calls + interpolation + add (tables in csrc/block.hip).
+ * 3 launches forward, 7 backward; train mode only; the same bits as two pdf_linbn_* calls + interpolation + add (tables in csrc/block.hip).
  * Arguments are validated before the first launch: PDF_ERR_BAD_ARG for null pointers / n < 1, PDF_ERR_UNSUPPORTED for widths outside
  * pdf_transition_up_supported (k1, k2 in {32, 64, 128, 256, 512}, o % 32 == 0, pdf_bn_supported(o)), eval mode or misaligned tensors. */
 int pdf_transition_up_supported(int k1, int k2, int o);
@@ -342,11 +343,24 @@ int pdf_transition_up_forward(long n1, int k1, long n2, int k2, int o, void *con
                               void *stream);
 int pdf_transition_up_backward(long n1, int k1, long n2, int k2, int o, void *const *p, int entry_base, int mma_input, void *stream);
 /* Two independent problems per launch (the building blocks of pdf_transition_up_*; tables in csrc/pointwise.hip, csrc/rowlin.hip): the
- * BatchNorm finalize of two norms, the BatchNorm(+ReLU) backward of two norms (3 launches), two weight gradients with ONE slab reduction.
+ * BatchNorm finalize of two norms, the BatchNorm(+ReLU) backward of two norms (3 launches), two weight gradients as ONE product launch
+ * (equal vector widths; PDFOPS_PAIR=0: one each) with ONE slab reduction.
  * Each problem keeps the grid of its single call, so the results are the bits of two single calls. */
 int pdf_bn_coef_from_partial2(int rows0, long n0, int c0, int rows1, long n1, int c1, void *const *p, float eps, float momentum, void *stream);
 int pdf_bn_act_backward2(long n0, int c0, long n1, int c1, void *const *p, int relu, void *stream);
 int pdf_rowlin_wgrad2(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, int mma_input, void *stream);
+/* Two Linear layers of one output width o with the statistics epilogue, y_i (n_i, o) = x_i (n_i, k_i) W_i^T + b_i and the rows of
+ * pdf_rowlin_forward's `partial`: one launch for the width pairs (k_0, k_1) = (32, 64), (64, 128), (128, 256), (256, 512), (512, 512), two
+ * otherwise (other widths or forms, mma_input != 0, PDFOPS_PAIR=0 in the environment) -- the bits of two pdf_rowlin_forward calls.  `paired`
+ * (nullable; also of the two entries below) receives 1 when the two products went out as one launch, 0 when as two.
+ * p[5 i + ..]: x, W (o, k_i), bias or null, y (written), partial (pdf_rowlin_partial_floats(n_i, o) floats, written). */
+int pdf_rowlin_forward_stats2(long n0, int k0, long n1, int k1, int o, void *const *p, int *paired, int mma_input, void *stream);
+/* Two input gradients gx_i (n_i, k_i) = g_i (n_i, o) W_i of Linear layers that share the output width o: one launch where both products run
+ * the same streaming kernel, two otherwise (and with PDFOPS_PAIR=0 in the environment) -- the bits of two pdf_rowlin_forward calls with
+ * transpose_w = 1.  p[3 i + ..]: g, W (o, k_i), gx (written; null: not computed). */
+int pdf_rowlin_dgrad2(long n0, int k0, long n1, int k1, int o, void *const *p, int *paired, int mma_input, void *stream);
+/* pdf_rowlin_wgrad2 with the same report. */
+int pdf_rowlin_wgrad2_paired(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, int *paired, int mma_input, void *stream);
 
 /* Row-weighted variants of the streaming Linear kernels and the bare BatchNorm-backward sums (building blocks of pdf_td_*). */
 int pdf_rowlin_forward_roww(long n, int k, int o, const float *x, long ldx, const float *w, int transpose_w, float *y, long ldy,

@@ -104,6 +104,9 @@ ENTRIES = {
     "pdf_rowlin_dgrad_bstats": ("s", "liiiplpplplpippip"),
     "pdf_rowlin_forward_bn": ("s", "liiplppppiplpppppffpip"),
     "pdf_rowlin_wgrad2": ("s", "liiliipip"),
+    "pdf_rowlin_forward_stats2": ("s", "liliippip"),
+    "pdf_rowlin_dgrad2": ("s", "liliippip"),
+    "pdf_rowlin_wgrad2_paired": ("s", "liiliippip"),
     "pdf_rowlin_forward_roww": ("s", "liiplpipliplip"),
     "pdf_rowlin_wgrad_roww": ("s", "liiplplpplpip"),
     # csrc/kpconv.hip

@@ -299,9 +299,11 @@ extern "C" int pdf_linbn_backward(long n, int k, int o, void *const *p, int trai
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // TransitionUp with two inputs (point_transformer_seg.py:162-167): out = relu(bn1(x1 W1^T + b1)) + interpolation(relu(bn2(x2 W2^T + b2)))
 // as ONE host call per direction.  The two Linear -> BatchNorm chains are independent of each other until the join, so their small
-// kernels run as two-problem launches (pdfops_common.h), and the norm applies, the interpolation and the add are one pass over z1 / z2
-// (gather_ops.hip: k_tu_join): 4 launches forward and 9 backward against 8 and 13 of two pdf_linbn_* nodes + interpolation + add.  Every
-// product, partial row and sum is formed by the same kernel body over the same grid as there: the results are the same bits.
+// kernels run as two-problem launches (pdfops_common.h), so do the two products of the forward and the two input-gradient and the two
+// weight-gradient products of the backward (rowlin.hip: pdf_rowlin_forward_stats_pair / pdf_rowlin_dgrad_pair / pdf_rowlin_wgrad_pair),
+// and the norm applies, the interpolation and the add are one pass over z1 / z2 (gather_ops.hip: k_tu_join): 3 launches forward and 7
+// backward against 8 and 13 of two pdf_linbn_* nodes + interpolation + add.  Every product, partial row and sum is formed by the same
+// kernel body over the same grid as there: the results are the same bits.
 // Train mode only (batch statistics); both norms share eps and momentum.
 extern "C" int pdf_transition_up_supported(int k1, int k2, int o) {
     return pdf_rowlin_streams(k1, o) && pdf_rowlin_streams(k2, o) && k1 % 32 == 0 && k2 % 32 == 0 && o % 32 == 0 && pdf_bn_supported(o);
@@ -328,16 +330,19 @@ extern "C" int pdf_transition_up_forward(long n1, int k1, long n2, int k2, int o
     PdfBnFinalize2 f;
     const long n[2] = {n1, n2};
     const int k[2] = {k1, k2};
+    PdfFwdStats2 l;
+    l.o = o;
     for (int i = 0; i < 2; ++i) {
         void *const *t = p + 7 * i;
-        float *z = (float *)p[17 + 3 * i], *partial = (float *)p[19 + 3 * i];
-        e << pdf_rowlin_forward(n[i], k[i], o, (const float *)t[0], k[i], (const float *)t[1], 0, (const float *)t[2], nullptr, nullptr, 0, z, o, 0, partial,
-                                mma_input, stream);
+        float *partial = (float *)p[19 + 3 * i];
+        l.n[i] = n[i]; l.k[i] = k[i]; l.x[i] = (const float *)t[0]; l.w[i] = (const float *)t[1]; l.bias[i] = (const float *)t[2];
+        l.y[i] = (float *)p[17 + 3 * i]; l.partial[i] = partial;
         f.partial[i] = partial; f.rows[i] = pdf_rowlin_partial_rows(n[i], k[i], o); f.nch[i] = o; f.count[i] = (double)n[i];
         f.gamma[i] = (const float *)t[3]; f.beta[i] = (const float *)t[4]; f.running_mean[i] = (float *)t[5]; f.running_var[i] = (float *)t[6];
         f.coef[i] = (float *)p[18 + 3 * i];
     }
     f.split = 0;
+    e << pdf_rowlin_forward_stats_pair(l, mma_input, stream);
     if (e.rc) return e.rc;
     e << pdf_bn_finalize2(f, eps, momentum, stream);
     e << pdf_tu_join(n1, o, (const float *)p[17], (const float *)p[18], (const float *)p[20], (const float *)p[21], (const int *)p[14],
@@ -375,10 +380,12 @@ extern "C" int pdf_transition_up_backward(long n1, int k1, long n2, int k2, int 
     }
     b.split = 0;
     e << pdf_bn_backward2(b, 1, stream);
-    for (int i = 0; i < 2; ++i)
-        if (p[13 + i])
-            e << pdf_rowlin_forward(n[i], o, k[i], b.gx[i], o, (const float *)p[4 + 4 * i], 1, nullptr, nullptr, nullptr, 0, (float *)p[13 + i], k[i], 0, nullptr,
-                                    mma_input, stream);
+    if (p[13] || p[14]) {
+        PdfDgrad2 d;
+        d.o = o;
+        for (int i = 0; i < 2; ++i) { d.n[i] = n[i]; d.k[i] = k[i]; d.g[i] = b.gx[i]; d.w[i] = (const float *)p[4 + 4 * i]; d.gx[i] = (float *)p[13 + i]; }
+        e << pdf_rowlin_dgrad_pair(d, mma_input, stream);
+    }
     e << pdf_rowlin_wgrad_pair(w, mma_input, stream);
     return e.rc;
 }

@@ -1218,7 +1218,13 @@ int backward_impl(LayerArgs A, float *sums, const int *inv_off, const int *inv_e
     if (mfma) flm::launch_b1(A, C, g1, s); else k_b1<C, K><<<grid, 64 * WPB, lds, s>>>(A);
     k_colsum<<<pdf_divup(b1_width<C>(), 16), RED_THREADS, 0, s>>>(A.partial, g1, b1_width<C>(), b1_width<C>(), S1, none);
     // g_xv[nb, c] = sum over the entries (i, j) with idx[i, j] == nb of g_out[i, c] * w[i, j, c mod C/8]   (no atomics, fixed order)
-    int rc = pdf_seg_sum_weighted_x(A.N, C, K, CS, A.gout, A.Wsm, A.bf16, inv_off, inv_entry, entry_base, gather_order, A.gxv, s);   // (destinations in Morton order: the g_out rows they share hit L2)
+    // fp32 rows on the matrix-core passes (levels 2-5): neither B2 nor B3 reads g_xv or overwrites g_out / Wsm, so this gather shares ONE
+    // launch with the g_xk gather after B3 (seg_gather.hip: pdf_seg_layer_pair; PDFOPS_PAIR=0 and the bfloat16 twins: two launches).  The
+    // level-1 forms (C = 32) keep two launches: there the pair itself gains 0.9 us, and B3 runs 3-5 us longer once the gather no longer
+    // sits between B1 and B2 (profiles/paired_launch_bench.json)
+    const bool pair_gathers = mfma && !A.bf16 && pdf_pair_launches();
+    int rc = PDF_OK;
+    if (!pair_gathers) rc = pdf_seg_sum_weighted_x(A.N, C, K, CS, A.gout, A.Wsm, A.bf16, inv_off, inv_entry, entry_base, gather_order, A.gxv, s);   // (destinations in Morton order: the g_out rows they share hit L2)
     if (rc != PDF_OK) return rc;
     A.sums = as_const(S1);
     const int g2 = mfma ? std::min(C == 64 ? 2 * grid : grid, pass_grid(B2, A.N, C == 512 ? 32 : (C == 256 ? 128 : (C == 64 ? 768 : grid)))) : grid;   // (C = 64: one slab, three workgroups per CU since round 6 -- the scratch holds grid * WPB rows)
@@ -1253,7 +1259,11 @@ int backward_impl(LayerArgs A, float *sums, const int *inv_off, const int *inv_e
         bc.col_g = b3_width<C>(); bc.out4 = S4;
     }
     k_colsum<<<pdf_divup(b3_width<C>(), 16) + (closed ? 1 : 0), RED_THREADS, 0, s>>>(A.partial, mfma ? g3 : (l1b3 ? g3l : gb3), b3_width<C>(), b3_pwidth<C>(), S3, bc);
-    rc = pdf_seg_sum_rows_x(A.N, C, A.GR, C, A.bf16, inv_off, inv_entry, entry_base, 1.0f, A.gxk, s);   // g_xk[nb] = sum of the g_r rows that gathered nb
+    rc = pair_gathers ? pdf_seg_layer_pair(A.N, C, K, CS, A.gout, A.Wsm, A.GR, inv_off, inv_entry, entry_base, gather_order, A.gxv, A.gxk, s) : PDF_ERR_UNSUPPORTED;
+    if (rc == PDF_ERR_UNSUPPORTED) {   // two launches (g_xv too, where it was held back for the pair)
+        rc = pair_gathers ? pdf_seg_sum_weighted_x(A.N, C, K, CS, A.gout, A.Wsm, A.bf16, inv_off, inv_entry, entry_base, gather_order, A.gxv, s) : PDF_OK;
+        if (rc == PDF_OK) rc = pdf_seg_sum_rows_x(A.N, C, A.GR, C, A.bf16, inv_off, inv_entry, entry_base, 1.0f, A.gxk, s);   // g_xk[nb] = sum of the g_r rows that gathered nb
+    }
     if (rc != PDF_OK) return rc;
     if (!closed) {
         A.sums = as_const(S3);

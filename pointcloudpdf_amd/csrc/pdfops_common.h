@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <atomic>
 #include "../../include/pdfops.h"
 
@@ -182,14 +183,36 @@ void launch_colsum2(PdfColsum2 q, hipStream_t s);
 }
 int pdf_bn_finalize2(PdfBnFinalize2 q, float eps, float momentum, void *stream);   // pointwise.hip
 int pdf_bn_backward2(PdfBnBwd2 q, int relu, void *stream);                         // pointwise.hip: reduce -> column sums -> apply, 3 launches
-// rowlin.hip: the two weight-gradient products (rl2::k_wg, one launch each, own workspace) followed by ONE two-problem slab reduction.
+// rowlin.hip: the two weight-gradient products (rl2::k_wg2: one launch, own workspace each) followed by ONE two-problem slab reduction.
 // Streaming shapes only (PDF_ERR_UNSUPPORTED otherwise).  ws[i]: pdf_rowlin_wgrad_ws_floats(n[i], k[i], o[i], 1) floats; db[i] may be null.
 struct PdfWgrad2 {
     long n[2]; int k[2], o[2];
     const float *g[2], *x[2];
     float *dw[2], *db[2], *ws[2];
 };
-int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream);
+int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream, int *paired = nullptr);   // paired: 1 = the products went out as one launch
+// rowlin.hip: the two input gradients gx_i (n_i, k_i) = g_i (n_i, o) W_i of Linear layers with one output width o, as one launch where the
+// streaming kernels allow it (two pdf_rowlin_forward launches otherwise: the same bits).  A null gx_i is not computed.
+struct PdfDgrad2 {
+    long n[2]; int k[2], o;
+    const float *g[2], *w[2];
+    float *gx[2];
+};
+int pdf_rowlin_dgrad_pair(const PdfDgrad2 &q, int mma_input, void *stream, int *paired = nullptr);
+// rowlin.hip: two Linear layers of one output width o with the statistics epilogue, y_i = x_i W_i^T + b_i and partial_i, as one launch where
+// the streaming kernels allow it (two pdf_rowlin_forward launches otherwise: the same bits).  bias[i] may be null.
+struct PdfFwdStats2 {
+    long n[2]; int k[2], o;
+    const float *x[2], *w[2], *bias[2];
+    float *y[2], *partial[2];
+};
+int pdf_rowlin_forward_stats_pair(const PdfFwdStats2 &q, int mma_input, void *stream, int *paired = nullptr);
+// seg_gather.hip: the fused layer's g_xv and g_xk gathers over one inverse table as one launch (fp32 rows; the bits of the two calls)
+int pdf_seg_layer_pair(long n, int c, int nsample, int w_c, const float *gout, const float *w, const float *gr, const int *inv_off, const int *inv_entry,
+                       int entry_base, const int *order, float *gxv, float *gxk, void *stream);
+// PDFOPS_PAIR=0: independent kernels that share a launch (rl2::k_fwd_stats2 / k_fwd2 / k_wg2, sg::k_seg_layer_pair) are issued one launch each, as before they were
+// paired -- the same bits, for A/B runs and tests.  Read at every call (host code does not run while a captured graph replays).
+static inline bool pdf_pair_launches() { const char *v = getenv("PDFOPS_PAIR"); return !(v && v[0] == '0'); }
 int pdf_rowlin_streams(int k, int o);   // rowlin.hip: (k, o) is a shape of the streaming kernels (rl2)
 // gather_ops.hip: out (n1, o) = relu(bn1(z1)) + interpolation(relu(bn2(z2))) over (n1, 3) tables, one pass
 int pdf_tu_join(long n1, int o, const float *z1, const float *coef1, const float *z2, const float *coef2, const int *idx, const float *weight,

@@ -208,6 +208,11 @@ void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias
 int try_wgrad_group(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx, const float *const *scale,
                     const float *const *shift, const int *relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s);
 void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s);
+int try_forward2(const long *n, int k, const int *o, const float *const *x, const float *const *w, int transpose_w, float *const *y, int mma, hipStream_t s);
+int try_forward_stats2(const long *n, const int *k, int o, const float *const *x, const float *const *w, const float *const *bias, float *const *y,
+                       float *const *partial, int mma, hipStream_t s);
+int try_wgrad_pair(const long *n, const int *k, const int *o, const float *const *g, const float *const *x, float *const *dw, float *const *db,
+                   float *const *ws, bool pair, int mma, hipStream_t s, RArgs *r);   // r[2]: the two slab reductions, left to the caller
 int stats_rows(long n);
 }  // namespace rl2
 
@@ -347,10 +352,13 @@ extern "C" int pdf_rowlin_wgrad(long n, int k, int o, const float *g, long ldg, 
     return pdf_launch_status();
 }
 
-// Two weight gradients of different shapes: the products as in pdf_rowlin_wgrad (rl2::k_wg, one launch each into its own workspace), then
+// Two weight gradients of different shapes: the products of pdf_rowlin_wgrad (rl2::wg_block, each problem with its own row split and
+// workspace) as ONE launch where both take the same vector width (rl2::k_wg2; PDFOPS_PAIR=0 or unequal widths: one launch each), then
 // ONE launch that reduces the slabs of both (rl2::k_slab_reduce2: each problem with the grid and the lane count of its own reduction --
-// the same sums in the same order).  Three launches instead of four.  Validates everything before the first launch.
-int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream) {
+// the same sums in the same order).  Two launches instead of four.  Validates everything before the first launch.  paired (nullable): receives
+// 1 when the two products went out as one launch, 0 when as two.
+int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream, int *paired) {
+    if (paired) *paired = 0;
     if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
     for (int i = 0; i < 2; ++i) {
         if (q.n[i] < 1 || q.k[i] < 1 || q.o[i] < 1 || !q.g[i] || !q.x[i] || !q.dw[i] || !q.ws[i]) return PDF_ERR_BAD_ARG;
@@ -359,17 +367,81 @@ int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream) {
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     rl2::RArgs r[2];
-    for (int i = 0; i < 2; ++i) {
-        const float *g = q.g[i];
-        float *dw = q.dw[i], *db = q.db[i];
-        if (!rl2::try_wgrad(q.n[i], q.k[i], q.o[i], 1, &g, q.o[i], q.x[i], q.k[i], nullptr, nullptr, 0, &dw, &db, q.ws[i], mma_input, s, nullptr, 0, &r[i]))
-            return PDF_ERR_UNSUPPORTED;   // (not reached: the conditions of try_wgrad are checked above)
-    }
+    const int took = rl2::try_wgrad_pair(q.n, q.k, q.o, q.g, q.x, q.dw, q.db, q.ws, pdf_pair_launches(), mma_input, s, r);
+    if (!took) return PDF_ERR_UNSUPPORTED;   // (not reached: the conditions of the setup are checked above)
+    if (paired) *paired = took == 2;
     rl2::launch_slab_reduce2(r[0], q.db[0] != nullptr, r[1], q.db[1] != nullptr, s);
     return pdf_launch_status();
 }
+
+// Two Linear layers of one output width in front of train-mode norms: y_i (n_i, o) = x_i (n_i, k_i) W_i^T + b_i with the statistics rows of
+// y_i in partial_i (pdf_rowlin_partial_rows(n_i, k_i, o) rows of [sum | sum of squares]), as ONE launch for the width pairs and forms
+// rl2::try_forward_stats2 covers (fp32 operands), else -- and with PDFOPS_PAIR=0 -- two pdf_rowlin_forward launches.  The same bits either
+// way.  paired (nullable): receives 1 when the products went out as one launch, 0 when as two.
+int pdf_rowlin_forward_stats_pair(const PdfFwdStats2 &q, int mma_input, void *stream, int *paired) {
+    if (paired) *paired = 0;
+    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (q.o < 1) return PDF_ERR_BAD_ARG;
+    for (int i = 0; i < 2; ++i)
+        if (q.n[i] < 1 || q.k[i] < 1 || !q.x[i] || !q.w[i] || !q.y[i] || !q.partial[i]) return PDF_ERR_BAD_ARG;
+    for (int i = 0; i < 2; ++i)   // (what pdf_rowlin_forward refuses with statistics, before the first launch)
+        if (rowlin_streams(q.k[i], q.o) && ((reinterpret_cast<uintptr_t>(q.x[i]) | reinterpret_cast<uintptr_t>(q.w[i]) | reinterpret_cast<uintptr_t>(q.y[i])) & 15))
+            return PDF_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (pdf_pair_launches() && rowlin_streams(q.k[0], q.o) && rowlin_streams(q.k[1], q.o) &&
+        rl2::try_forward_stats2(q.n, q.k, q.o, q.x, q.w, q.bias, q.y, q.partial, mma_input, s)) {
+        if (paired) *paired = 1;
+        return pdf_launch_status();
+    }
+    int rc = 0;
+    for (int i = 0; i < 2 && rc == 0; ++i)
+        rc = pdf_rowlin_forward(q.n[i], q.k[i], q.o, q.x[i], q.k[i], q.w[i], 0, q.bias[i], nullptr, nullptr, 0, q.y[i], q.o, 0, q.partial[i], mma_input, stream);
+    return rc;
+}
+// p[]: per problem i, p[5 i + ..]: 0 x (n, k) 1 W (o, k) 2 bias (o) or null 3 y (n, o; written) 4 partial (pdf_rowlin_partial_floats(n, o); written)
+extern "C" int pdf_rowlin_forward_stats2(long n0, int k0, long n1, int k1, int o, void *const *p, int *paired, int mma_input, void *stream) {
+    if (!p) return PDF_ERR_BAD_ARG;
+    PdfFwdStats2 q;
+    q.n[0] = n0; q.k[0] = k0; q.n[1] = n1; q.k[1] = k1; q.o = o;
+    for (int i = 0; i < 2; ++i) {
+        void *const *t = p + 5 * i;
+        q.x[i] = (const float *)t[0]; q.w[i] = (const float *)t[1]; q.bias[i] = (const float *)t[2]; q.y[i] = (float *)t[3]; q.partial[i] = (float *)t[4];
+    }
+    return pdf_rowlin_forward_stats_pair(q, mma_input, stream, paired);
+}
+
+// Two input gradients gx_i (n_i, k_i) = g_i (n_i, o) W_i, W_i (o, k_i) row-major, that reduce over the same o (the two Linear layers of a
+// TransitionUp join): ONE launch where both products run the same streaming kernel (rl2::try_forward2), else -- and with PDFOPS_PAIR=0 --
+// two pdf_rowlin_forward launches.  The same bits either way.  A null gx_i is not computed.  Validates everything before the first launch.
+// paired (nullable): receives 1 when the products went out as one launch (fp32 operands, same slab width and form), 0 when as two.
+int pdf_rowlin_dgrad_pair(const PdfDgrad2 &q, int mma_input, void *stream, int *paired) {
+    if (paired) *paired = 0;
+    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (q.o < 1) return PDF_ERR_BAD_ARG;
+    for (int i = 0; i < 2; ++i)
+        if (q.n[i] < 1 || q.k[i] < 1 || !q.g[i] || !q.w[i]) return PDF_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (q.gx[0] && q.gx[1] && pdf_pair_launches() && rowlin_streams(q.o, q.k[0]) && rowlin_streams(q.o, q.k[1]) &&
+        rl2::try_forward2(q.n, q.o, q.k, q.g, q.w, 1, q.gx, mma_input, s)) {
+        if (paired) *paired = 1;
+        return pdf_launch_status();
+    }
+    int rc = 0;
+    for (int i = 0; i < 2 && rc == 0; ++i)
+        if (q.gx[i]) rc = pdf_rowlin_forward(q.n[i], q.o, q.k[i], q.g[i], q.o, q.w[i], 1, nullptr, nullptr, nullptr, 0, q.gx[i], q.k[i], 0, nullptr, mma_input, stream);
+    return rc;
+}
+// p[]: per problem i, p[3 i + ..]: 0 g (n, o) 1 W (o, k) 2 gx (n, k; written) or null (not computed)
+extern "C" int pdf_rowlin_dgrad2(long n0, int k0, long n1, int k1, int o, void *const *p, int *paired, int mma_input, void *stream) {
+    if (!p) return PDF_ERR_BAD_ARG;
+    PdfDgrad2 q;
+    q.n[0] = n0; q.k[0] = k0; q.n[1] = n1; q.k[1] = k1; q.o = o;
+    for (int i = 0; i < 2; ++i) { q.g[i] = (const float *)p[3 * i]; q.w[i] = (const float *)p[3 * i + 1]; q.gx[i] = (float *)p[3 * i + 2]; }
+    return pdf_rowlin_dgrad_pair(q, mma_input, stream, paired);
+}
 // p[]: per problem i, p[5 i + ..]: 0 g (n, o) 1 x (n, k) 2 dW (o, k; written) 3 db (o; written) or null 4 ws (pdf_rowlin_wgrad_ws_floats(n, k, o, 1))
-extern "C" int pdf_rowlin_wgrad2(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, int mma_input, void *stream) {
+// (pdf_rowlin_wgrad2_paired: the same call; *paired receives 1 when the two products went out as one launch, 0 when as two)
+extern "C" int pdf_rowlin_wgrad2_paired(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, int *paired, int mma_input, void *stream) {
     if (!p) return PDF_ERR_BAD_ARG;
     PdfWgrad2 q;
     q.n[0] = n0; q.k[0] = k0; q.o[0] = o0; q.n[1] = n1; q.k[1] = k1; q.o[1] = o1;
@@ -377,7 +449,10 @@ extern "C" int pdf_rowlin_wgrad2(long n0, int k0, int o0, long n1, int k1, int o
         void *const *t = p + 5 * i;
         q.g[i] = (const float *)t[0]; q.x[i] = (const float *)t[1]; q.dw[i] = (float *)t[2]; q.db[i] = (float *)t[3]; q.ws[i] = (float *)t[4];
     }
-    return pdf_rowlin_wgrad_pair(q, mma_input, stream);
+    return pdf_rowlin_wgrad_pair(q, mma_input, stream, paired);
+}
+extern "C" int pdf_rowlin_wgrad2(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, int mma_input, void *stream) {
+    return pdf_rowlin_wgrad2_paired(n0, k0, o0, n1, k1, o1, p, nullptr, mma_input, stream);
 }
 
 // Several Linear layers over the same rows in one launch (channel widths 32..256, see rowlin2.hip):

@@ -9,4 +9,6 @@ template int try_wgrad_mp<2>(long, int, int, int, const float *const *, long, co
                              float *const *, float *const *, float *, hipStream_t, const float *, long, RArgs *);
 template int try_wgrad_group_mp<2>(long, int, int, int, const float *const *, long, const float *const *, long, const float *const *, const float *const *, const int *,
                                    float *const *, float *const *, float *, hipStream_t);
+template int try_wgrad_pair_mp<2>(const long *, const int *, const int *, const float *const *, const float *const *, float *const *, float *const *,
+                                  float *const *, bool, hipStream_t, RArgs *);
 }  // namespace rl2

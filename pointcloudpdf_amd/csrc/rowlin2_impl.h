@@ -86,16 +86,18 @@ static inline int fwd_row_blocks(long n) {
     return (int)(b < 1 ? 1 : (b > FWD_CAP ? FWD_CAP : b));
 }
 
+// One workgroup of k_fwd: (bx, by) = its block id in the grid of ITS problem, gdx = that grid's row blocks.  The kernels below hand it
+// blockIdx / gridDim (single launch) or the coordinates of one of two problems that share a launch (k_fwd2).
 template <int K, int NOB, int NIN, bool PRE, int ST, int MP>   // ST: 0 = no statistics, 1 = [sum | sum of squares] of the output, 2 = BatchNorm-backward sums (FwdArgs); MP: Mma
-__global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
+__device__ __forceinline__ void fwd_block(const FwdArgs &a, const unsigned bx, const unsigned by, const unsigned gdx) {
     typedef typename Mma<MP>::frag wfrag;
     constexpr bool STATS = ST != 0;
     constexpr int NJ = K / 16;
     constexpr bool COEF_REGS = K <= 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, kq = lane >> 4;
-    if (ST == 1 && a.ho_gran && blockIdx.x == 0 && blockIdx.y == 0) pdf_handoff_zero(a.ho_gran, a.O, a.ho_sync);
-    const int gcol0 = blockIdx.y * NOB * 16;   // column over the concatenated outputs; a 16-column block never straddles two
+    if (ST == 1 && a.ho_gran && bx == 0 && by == 0) pdf_handoff_zero(a.ho_gran, a.O, a.ho_sync);
+    const int gcol0 = (int)by * NOB * 16;   // column over the concatenated outputs; a 16-column block never straddles two
     int outi[NOB], colb[NOB];
 #pragma unroll
     for (int ob = 0; ob < NOB; ++ob) { outi[ob] = (gcol0 + ob * 16) / a.O; colb[ob] = gcol0 + ob * 16 - outi[ob] * a.O; }
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
     constexpr int XB0 = NJ < 16 ? NJ : 16;
     constexpr int XB = (K == 256 && NIN == 3) ? 4 : ((ST != 0 && NOB > 1 && NIN * NOB * NJ * 4 >= 128) ? ((PRE && K == 128) ? 2 : XB0 / 2) : XB0);
     const long ntiles = (a.N + 15) / 16;
-    for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
+    for (long tile = (long)bx * 4 + wave; tile < ntiles; tile += (long)gdx * 4) {
         const long n = tile * 16 + li;
         const bool valid = n < a.N;
         f32x4 acc[NOB];
@@ -241,12 +243,16 @@ __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
         __syncthreads();
         const int t = threadIdx.x;
         if (t < NOB * 16) {
-            float *row = a.partial + (size_t)blockIdx.x * 2 * a.O;
+            float *row = a.partial + (size_t)bx * 2 * a.O;
             row[gcol0 + t] = red[0][0][t] + red[1][0][t] + red[2][0][t] + red[3][0][t];      // STATS: single output, gcol0 == column
             const float ss = red[0][1][t] + red[1][1][t] + red[2][1][t] + red[3][1][t];
             row[a.O + gcol0 + t] = ST == 2 ? ss * a.bcoef[3 * (long)a.O + gcol0 + t] : ss;
         }
     }
+}
+template <int K, int NOB, int NIN, bool PRE, int ST, int MP>
+__global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
+    fwd_block<K, NOB, NIN, PRE, ST, MP>(a, blockIdx.x, blockIdx.y, gridDim.x);
 }
 
 // The group form of k_fwd, for launches with few row tiles and many column blocks (levels 3-5: the three-output q / k / v product, the
@@ -267,7 +273,7 @@ constexpr int GROUP_GN = 2;
 template <int K, int GN, int NIN, int MP> constexpr int group_lds_bytes() { return NIN * GN * (K / 16) * 64 * (int)sizeof(typename Mma<MP>::frag); }
 
 template <int K, int GN, int NIN, bool PRE, int ST, int MP>
-__global__ __launch_bounds__(256, 2) void k_fwd_group(FwdArgs a) {   // (at least two waves per SIMD: the images of 16-96 KB leave room for two workgroups per CU)
+__device__ __forceinline__ void fwd_group_block(const FwdArgs &a, const unsigned bx, const unsigned by, const unsigned gdx) {   // (block coordinates: as fwd_block)
     typedef typename Mma<MP>::frag wfrag;
     constexpr bool STATS = ST != 0;
     constexpr int NJ = K / 16;
@@ -276,8 +282,8 @@ __global__ __launch_bounds__(256, 2) void k_fwd_group(FwdArgs a) {   // (at leas
     wfrag *Wl = reinterpret_cast<wfrag *>(group_lds);   // [NIN][GN][NJ][64]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, kq = lane >> 4;
-    if (ST == 1 && a.ho_gran && blockIdx.x == 0 && blockIdx.y == 0) pdf_handoff_zero(a.ho_gran, a.O, a.ho_sync);
-    const int gcol0 = blockIdx.y * GN * 16;
+    if (ST == 1 && a.ho_gran && bx == 0 && by == 0) pdf_handoff_zero(a.ho_gran, a.O, a.ho_sync);
+    const int gcol0 = (int)by * GN * 16;
     int outi[GN], colb[GN];
 #pragma unroll
     for (int ob = 0; ob < GN; ++ob) { outi[ob] = (gcol0 + ob * 16) / a.O; colb[ob] = gcol0 + ob * 16 - outi[ob] * a.O; }
@@ -318,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_group(FwdArgs a) {   // (at leas
     const float relu_lo = a.relu ? 0.f : -INFINITY;
     constexpr int XB = 8, NBJ = NJ / XB, NB = NIN * NBJ;   // batches of XB steps; batch b + 1 is in flight while batch b is multiplied
     const long ntiles = (a.N + 15) / 16;
-    for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
+    for (long tile = (long)bx * 4 + wave; tile < ntiles; tile += (long)gdx * 4) {
         const long n = tile * 16 + li;
         const bool valid = n < a.N;
         const long row = valid ? n : 0;   // (rows past the end read row 0 and never store)
@@ -405,11 +411,53 @@ __global__ __launch_bounds__(256, 2) void k_fwd_group(FwdArgs a) {   // (at leas
         __syncthreads();
         const int t = threadIdx.x;
         if (t < GN * 16) {
-            float *prow = a.partial + (size_t)blockIdx.x * 2 * a.O;
+            float *prow = a.partial + (size_t)bx * 2 * a.O;
             prow[gcol0 + t] = red[0][0][t] + red[1][0][t] + red[2][0][t] + red[3][0][t];
             const float ss = red[0][1][t] + red[1][1][t] + red[2][1][t] + red[3][1][t];
             prow[a.O + gcol0 + t] = ST == 2 ? ss * a.bcoef[3 * (long)a.O + gcol0 + t] : ss;
         }
+    }
+}
+template <int K, int GN, int NIN, bool PRE, int ST, int MP>
+__global__ __launch_bounds__(256, 2) void k_fwd_group(FwdArgs a) {   // (at least two waves per SIMD: the images of 16-96 KB leave room for two workgroups per CU)
+    fwd_group_block<K, GN, NIN, PRE, ST, MP>(a, blockIdx.x, blockIdx.y, gridDim.x);
+}
+
+// Two plain products (one input, one output, no prologue, no statistics) of ONE reduction width in one launch: the input gradients
+// gz_1 W_1 and gz_2 W_2 of a TransitionUp join reduce over the same o and differ in rows, output width and pointers only.  Workgroups
+// below `split` are problem 0's grid (x fastest, as the hardware numbers a two-dimensional grid), the rest problem 1's; each runs
+// fwd_block / fwd_group_block with the coordinates and the extent of its own grid.
+struct FwdArgs2 { FwdArgs a[2]; unsigned gx[2], split; };
+template <int K, int NOB, int MP>
+__global__ __launch_bounds__(256) void k_fwd2(FwdArgs2 q) {
+    const int i = blockIdx.x >= q.split ? 1 : 0;
+    const unsigned b = blockIdx.x - (i ? q.split : 0u), gx = q.gx[i];
+    fwd_block<K, NOB, 1, false, 0, MP>(q.a[i], b % gx, b / gx, gx);
+}
+template <int K, int GN, int MP>
+__global__ __launch_bounds__(256, 2) void k_fwd_group2(FwdArgs2 q) {
+    const int i = blockIdx.x >= q.split ? 1 : 0;
+    const unsigned b = blockIdx.x - (i ? q.split : 0u), gx = q.gx[i];
+    fwd_group_block<K, GN, 1, false, 0, MP>(q.a[i], b % gx, b / gx, gx);
+}
+
+// Two products with the statistics epilogue (one input, one output, bias, no prologue) of DIFFERENT reduction widths in one launch: the
+// two Linear layers in front of a TransitionUp join's norms, x1 W1^T (K0) and x2 W2^T (K1).  Each problem runs the body of its own single
+// launch -- slab form with NB column blocks per wave, or group form with NB blocks per workgroup -- over its own grid, problem 0's
+// workgroups first (x fastest); the partial rows are indexed by each problem's own row block.  The branch is uniform per workgroup and
+// every barrier stays inside one body.  Dynamic LDS: the larger weight image of the group-form problems.
+template <int K, int NB, bool GROUP, int MP>
+__device__ __forceinline__ void fwd_stats_block(const FwdArgs &a, unsigned bx, unsigned by, unsigned gdx) {
+    if constexpr (GROUP) fwd_group_block<K, NB, 1, false, 1, MP>(a, bx, by, gdx);
+    else fwd_block<K, NB, 1, false, 1, MP>(a, bx, by, gdx);
+}
+template <int K0, int NB0, bool G0, int K1, int NB1, bool G1, int MP>
+__global__ __launch_bounds__(256, (G0 || G1) ? 2 : 1) void k_fwd_stats2(FwdArgs2 q) {
+    if (blockIdx.x < q.split) {
+        fwd_stats_block<K0, NB0, G0, MP>(q.a[0], blockIdx.x % q.gx[0], blockIdx.x / q.gx[0], q.gx[0]);
+    } else {
+        const unsigned b = blockIdx.x - q.split;
+        fwd_stats_block<K1, NB1, G1, MP>(q.a[1], b % q.gx[1], b / q.gx[1], q.gx[1]);
     }
 }
 
@@ -434,8 +482,9 @@ template <int VW> struct Vec;
 template <> struct Vec<2> { typedef float type __attribute__((ext_vector_type(2))); };
 template <> struct Vec<4> { typedef float type __attribute__((ext_vector_type(4))); };
 
+// One workgroup of k_wg: (bx, by, bz) = its block id in the grid of ITS problem, (gdx, gdy) = that grid's extents (block coordinates: as fwd_block).
 template <int VW, bool PRE, bool RW, int MP>   // RW: per-row weight of G (a.roww); MP: Mma
-__global__ __launch_bounds__(256) void k_wg(WArgs a) {
+__device__ __forceinline__ void wg_block(const WArgs &a, const unsigned bx, const unsigned by, const unsigned bz, const unsigned gdx, const unsigned gdy) {
     typedef typename Vec<VW>::type vec;
     constexpr int B = 16 * VW;   // block edge of dW
     __shared__ float red[4][B * B];   // one (16 VW)^2 block per wave: plain stores, then a 4-way sum (LDS atomics cost 20 us here)
@@ -443,14 +492,14 @@ __global__ __launch_bounds__(256) void k_wg(WArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, nq = lane >> 4;
     const int nkb = a.K / B;
-    const int ob = (blockIdx.y / nkb) * B, kb = (blockIdx.y % nkb) * B;
-    const float *G = a.G[blockIdx.z];
-    const float *X = (PRE && a.per_z) ? a.Xz[blockIdx.z] : a.X;
+    const int ob = ((int)by / nkb) * B, kb = ((int)by % nkb) * B;
+    const float *G = a.G[bz];
+    const float *X = (PRE && a.per_z) ? a.Xz[bz] : a.X;
     vec sc, sh;
     bool relu = a.relu != 0;
     if (PRE) {
-        const float *scp = a.per_z ? a.scalez[blockIdx.z] : a.scale, *shp = a.per_z ? a.shiftz[blockIdx.z] : a.shift;
-        if (a.per_z) relu = scp != nullptr && a.reluz[blockIdx.z] != 0;
+        const float *scp = a.per_z ? a.scalez[bz] : a.scale, *shp = a.per_z ? a.shiftz[bz] : a.shift;
+        if (a.per_z) relu = scp != nullptr && a.reluz[bz] != 0;
         if (scp) {   // (uniform per workgroup)
             sc = *reinterpret_cast<const vec *>(scp + kb + VW * li);
             sh = *reinterpret_cast<const vec *>(shp + kb + VW * li);
@@ -468,7 +517,7 @@ __global__ __launch_bounds__(256) void k_wg(WArgs a) {
 #pragma unroll
         for (int c2 = 0; c2 < VW; ++c2) acc[c][c2] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const long rb = (long)blockIdx.x * a.rows_per_block;
+    const long rb = (long)bx * a.rows_per_block;
     const long re = rb + a.rows_per_block < a.N ? rb + a.rows_per_block : a.N;
     for (long r0 = rb + 16 * wave; r0 < re; r0 += 64) {
         // the eight (twelve) loads of a trip first, nothing conditional between them: with the row weight behind `if (a.roww)` and the
@@ -530,7 +579,7 @@ __global__ __launch_bounds__(256) void k_wg(WArgs a) {
         for (int c2 = 0; c2 < VW; ++c2)
 #pragma unroll
             for (int r = 0; r < 4; ++r) red[wave][(VW * (4 * nq + r) + c) * B + VW * li + c2] = acc[c][c2][r];
-    float *db = a.db[blockIdx.z];
+    float *db = a.db[bz];
     const bool want_db = db && kb == 0;
     if (want_db) {
 #pragma unroll
@@ -542,11 +591,24 @@ __global__ __launch_bounds__(256) void k_wg(WArgs a) {
         }
     }
     __syncthreads();
-    float *slab = a.slab + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (B * B);
+    float *slab = a.slab + (((size_t)bz * gdy + by) * gdx + bx) * (B * B);
     for (int e = threadIdx.x; e < B * B; e += 256) slab[e] = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
     if (want_db && threadIdx.x < B)
-        a.bslab[(((size_t)blockIdx.z * (a.O / B) + ob / B) * gridDim.x + blockIdx.x) * B + threadIdx.x] =
+        a.bslab[(((size_t)bz * (a.O / B) + ob / B) * gdx + bx) * B + threadIdx.x] =
             (redb[0][threadIdx.x] + redb[1][threadIdx.x]) + (redb[2][threadIdx.x] + redb[3][threadIdx.x]);
+}
+template <int VW, bool PRE, bool RW, int MP>
+__global__ __launch_bounds__(256) void k_wg(WArgs a) {
+    wg_block<VW, PRE, RW, MP>(a, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
+}
+// Two single-gradient products without prologue or row weight in one launch (the two weight gradients of a TransitionUp join): each
+// problem with its own K, O, row split and workspace; workgroups below `split` are problem 0's grid (x fastest), the rest problem 1's.
+struct WArgs2 { WArgs a[2]; unsigned gx[2], gy[2], split; };
+template <int VW, int MP>
+__global__ __launch_bounds__(256) void k_wg2(WArgs2 q) {
+    const int i = blockIdx.x >= q.split ? 1 : 0;
+    const unsigned b = blockIdx.x - (i ? q.split : 0u), gx = q.gx[i];
+    wg_block<VW, false, false, MP>(q.a[i], b % gx, b / gx, 0u, gx, q.gy[i]);
 }
 
 // Sum of the `split` slabs of every dW block (and bias block) in a fixed order: lane l of an element adds slabs l, l + L, l + 2L, ...,
@@ -705,6 +767,13 @@ static bool launch_fwd_group(const FwdArgs &a, int blocks, int gx, hipStream_t s
     return pre ? launch_group_kernel<K, GN, NIN, true, 0, MP>(a, grid, s) : launch_group_kernel<K, GN, NIN, false, 0, MP>(a, grid, s);
 }
 
+// Row blocks of a launch with `nslabs` column slabs (launch_fwd below: what `capped` is for, and the measurements behind 512).
+static int fwd_grid_rows(long n, int nslabs, bool capped) {
+    static const int total = [] { const char *v = getenv("PDFOPS_RL_BLOCKS"); const int x = v ? atoi(v) : 0; return x > 0 ? x : 512; }();
+    const int gx = fwd_row_blocks(n);
+    return capped ? std::max(1, std::min(gx, std::max(8, total / std::max(nslabs, 1)))) : gx;
+}
+
 template <int K, int NOB, int NIN, int MP>
 static int launch_fwd(const FwdArgs &a, int nslabs, hipStream_t s) {   // returns the number of row blocks (= partial rows written)
     const bool pre = a.scale != nullptr, stats = a.partial != nullptr, bst = stats && a.bx != nullptr;
@@ -714,9 +783,7 @@ static int launch_fwd(const FwdArgs &a, int nslabs, hipStream_t s) {   // return
     // rows are indexed by row block and sized by pdf_rowlin_partial_rows.)
     // Measured (PDFOPS_RL_BLOCKS = total workgroups aimed at): 512 -> q / k / v product at 3,124 x 256: 41 -> 31 us, three-input dgrad 36 -> 30 us,
     // 780 x 512: 54 -> 46 us, single-slab shapes unchanged; 384 and below lose on the large levels, 1024 and above change nothing.
-    static const int total = [] { const char *v = getenv("PDFOPS_RL_BLOCKS"); const int x = v ? atoi(v) : 0; return x > 0 ? x : 512; }();
-    int gx = fwd_row_blocks(a.N);
-    if (!stats || bst) gx = std::max(1, std::min(gx, std::max(8, total / std::max(nslabs, 1))));   // (bst: the caller is told the row count)
+    const int gx = fwd_grid_rows(a.N, nslabs, !stats || bst);   // (bst: the caller is told the row count)
     if constexpr (K >= 128 && NIN != 2) {
         if (group_form_wanted(a, K, nslabs * NOB) && launch_fwd_group<K, GROUP_GN, NIN, MP>(a, nslabs * NOB, gx, s)) return gx;
     }
@@ -737,6 +804,19 @@ static int launch_fwd(const FwdArgs &a, int nslabs, hipStream_t s) {   // return
 #ifdef RL2_MAIN_TU
 long stats_rows_floats(long n, int o) { return (long)fwd_row_blocks(n) * 2 * o; }
 #endif
+
+// 16-column blocks per wave of the one-input kernels for (k, cols): the widest instantiated slab that divides the columns (0: k is not covered)
+static int fwd_nob1(int k, int cols, bool stats, bool bst) {
+    const auto fits = [cols](int nob) { return cols % (nob * 16) == 0; };
+    switch (k) {
+    case 32: return (!stats && fits(6)) ? 6 : (fits(2) ? 2 : 1);   // (statistics: at most 2 column blocks per wave)
+    case 64: return fits(4) ? 4 : 1;
+    case 128: { const int wide = bst ? 2 : 4; return fits(wide) ? wide : 1; }   // (ST == 2 with 4 column blocks: 305 registers, one wave per SIMD)
+    case 256: return fits(2) ? 2 : 1;
+    case 512: return 1;
+    default: return 0;
+    }
+}
 
 // returns 1 when a streaming kernel took the job, 0 when the shape is not covered (caller falls back to the tiled kernel)
 template <int MP>
@@ -772,12 +852,18 @@ int try_forward_mp(long n, int k, int o, int nin, int nout, const float *const *
         if (partial_rows) *partial_rows = r_; \
         return 1; } } while (0)
     if (nin == 1) {
-        switch (k) {
-        case 32: if (!partial) PDF_RL2(32, 6, 1); PDF_RL2(32, 2, 1); PDF_RL2(32, 1, 1); break;   // (statistics: at most 2 column blocks per wave)
-        case 64: PDF_RL2(64, 4, 1); PDF_RL2(64, 1, 1); break;
-        case 128: if (!bx) PDF_RL2(128, 4, 1); else PDF_RL2(128, 2, 1); PDF_RL2(128, 1, 1); break;   // (ST == 2 with 4 column blocks: 305 registers, one wave per SIMD)
-        case 256: PDF_RL2(256, 2, 1); PDF_RL2(256, 1, 1); break;
-        case 512: PDF_RL2(512, 1, 1); break;
+        switch (k * 8 + fwd_nob1(k, cols, partial != nullptr, bx != nullptr)) {
+        case 32 * 8 + 6: PDF_RL2(32, 6, 1); break;
+        case 32 * 8 + 2: PDF_RL2(32, 2, 1); break;
+        case 32 * 8 + 1: PDF_RL2(32, 1, 1); break;
+        case 64 * 8 + 4: PDF_RL2(64, 4, 1); break;
+        case 64 * 8 + 1: PDF_RL2(64, 1, 1); break;
+        case 128 * 8 + 4: PDF_RL2(128, 4, 1); break;
+        case 128 * 8 + 2: PDF_RL2(128, 2, 1); break;
+        case 128 * 8 + 1: PDF_RL2(128, 1, 1); break;
+        case 256 * 8 + 2: PDF_RL2(256, 2, 1); break;
+        case 256 * 8 + 1: PDF_RL2(256, 1, 1); break;
+        case 512 * 8 + 1: PDF_RL2(512, 1, 1); break;
         default: break;
         }
     } else if (nin == 2) {   // two 512-wide column windows of one 1024-wide input (ldw): ONE accumulation chain over both, bias at the end
@@ -795,41 +881,193 @@ int try_forward_mp(long n, int k, int o, int nin, int nout, const float *const *
     return 0;
 }
 
+template <int K, int MP>
+static bool launch_fwd_group2(const FwdArgs2 &q, unsigned total, hipStream_t s) {
+    constexpr int lds = group_lds_bytes<K, GROUP_GN, 1, MP>();
+    static PdfLdsLimit site;
+    if (!pdf_lds_limit_raised(site, reinterpret_cast<const void *>(&k_fwd_group2<K, GROUP_GN, MP>), lds)) return false;
+    k_fwd_group2<K, GROUP_GN, MP><<<total, 256, lds, s>>>(q);
+    return true;
+}
+
+// Two plain products Y_i (n_i, o_i) = X_i (n_i, k) Wt_i of ONE reduction width in one launch (k_fwd2 / k_fwd_group2; transpose_w as in
+// try_forward_mp).  Paired is what a TransitionUp join reaches: both problems on the same kernel, i.e. the same slab width and the same
+// form, at the widths instantiated below.  Each problem keeps the row blocks and column slabs launch_fwd gives it; the workgroups of the
+// problem with more tiles per workgroup come first.  Returns 1 when the pair was launched; 0 when nothing was launched -- the caller
+// issues two single launches, which form the same bits.  Instantiated for fp32 operands only (rowlin2.hip: reduced-precision products
+// take the two launches).
 template <int MP>
-int try_wgrad_mp(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
-                 const float *shift, int relu, float *const *dw, float *const *db, float *ws, hipStream_t s, const float *roww, long rws,
-                 RArgs *defer) {   // defer: the slab reduction is not launched, its arguments are handed back (launch_slab_reduce2)
-    if (ng < 1 || ng > 3 || !ws) return 0;
+int try_forward2_mp(const long *n, int k, const int *o, const float *const *x, const float *const *w, int transpose_w, float *const *y, hipStream_t s) {
+    FwdArgs u[2];
+    int nob[2], gx[2], gy[2];
+    bool group[2];
+    long trips[2];
+    for (int i = 0; i < 2; ++i) {
+        if (n[i] < 1 || o[i] < 16 || (o[i] & 15) || !aligned16(x[i]) || !aligned16(w[i]) || !aligned16(y[i])) return 0;
+        nob[i] = fwd_nob1(k, o[i], false, false);
+        if (!nob[i]) return 0;
+        FwdArgs &a = u[i];
+        a.N = n[i]; a.O = o[i]; a.ldx = k; a.ldy = o[i]; a.scale = a.shift = nullptr; a.relu = 0; a.accumulate = 0; a.partial = nullptr;
+        a.roww = nullptr; a.rws = 0; a.bx = nullptr; a.ldb = 0; a.bcoef = nullptr; a.brelu = 0; a.ho_gran = nullptr; a.ho_sync = nullptr;
+        a.wso = transpose_w ? 1 : k; a.wsk = transpose_w ? o[i] : 1;
+        for (int t = 0; t < 3; ++t) { a.X[t] = t ? nullptr : x[i]; a.W[t] = t ? nullptr : w[i]; a.bias[t] = nullptr; a.Y[t] = t ? nullptr : y[i]; }
+        const int nslabs = o[i] / (nob[i] * 16);
+        gx[i] = fwd_grid_rows(n[i], nslabs, true);
+        group[i] = k >= 128 && group_form_wanted(a, k, nslabs * nob[i]);
+        gy[i] = group[i] ? nslabs * nob[i] / GROUP_GN : nslabs;
+        trips[i] = ((n[i] + 15) / 16 + 4L * gx[i] - 1) / (4L * gx[i]);
+    }
+    if (nob[0] != nob[1] || group[0] != group[1]) return 0;
+    const int first = trips[1] > trips[0] ? 1 : 0;
+    FwdArgs2 q;
+    for (int j = 0; j < 2; ++j) { const int i = j ? 1 - first : first; q.a[j] = u[i]; q.gx[j] = (unsigned)gx[i]; }
+    q.split = (unsigned)(gx[first] * gy[first]);
+    const unsigned total = q.split + (unsigned)(gx[1 - first] * gy[1 - first]);
+    if (group[0]) {
+        switch (k) {
+        case 128: return launch_fwd_group2<128, MP>(q, total, s) ? 1 : 0;
+        case 256: return launch_fwd_group2<256, MP>(q, total, s) ? 1 : 0;
+        case 512: return launch_fwd_group2<512, MP>(q, total, s) ? 1 : 0;
+        default: return 0;
+        }
+    }
+    switch (k * 8 + nob[0]) {   // (slab form: the joins at o = 32 and 64; wider joins reach the slab form only above GROUP_MAX_ROWS rows: two launches)
+    case 32 * 8 + 2: k_fwd2<32, 2, MP><<<total, 256, 0, s>>>(q); return 1;
+    case 64 * 8 + 4: k_fwd2<64, 4, MP><<<total, 256, 0, s>>>(q); return 1;
+    default: return 0;
+    }
+}
+
+template <int K0, int NB0, bool G0, int K1, int NB1, bool G1, int MP>
+static bool launch_fwd_stats2(const FwdArgs2 &q, unsigned total, hipStream_t s) {
+    constexpr int lds0 = G0 ? group_lds_bytes<K0, NB0, 1, MP>() : 0, lds1 = G1 ? group_lds_bytes<K1, NB1, 1, MP>() : 0, lds = lds0 > lds1 ? lds0 : lds1;
+    if (lds) {
+        static PdfLdsLimit site;
+        if (!pdf_lds_limit_raised(site, reinterpret_cast<const void *>(&k_fwd_stats2<K0, NB0, G0, K1, NB1, G1, MP>), lds)) return false;
+    }
+    k_fwd_stats2<K0, NB0, G0, K1, NB1, G1, MP><<<total, 256, lds, s>>>(q);
+    return true;
+}
+
+// Y_i (n_i, o) = X_i (n_i, k_i) W_i^T + bias_i with the statistics rows partial_i [fwd_row_blocks(n_i)][2 o], i = 0, 1, in ONE launch
+// (k_fwd_stats2).  Paired are the width pairs of the model's joins -- (32, 64), (64, 128), (128, 256), (256, 512), (512, 512) -- in the forms
+// launch_fwd gives those widths at the model's row counts.  Problem 0's workgroups always come first: the two problems are different
+// template instantiations, so "the longer problem first" would take a mirrored kernel per pair; at levels 4-5, where problem 1 (K = 512)
+// has the longer chain per workgroup, both grids together are under two workgroups per CU and start at once, so the order decides nothing
+// there.  Returns 1 when the pair was launched; 0 when nothing was launched -- the caller issues two single launches, which form the
+// same bits.  Instantiated for fp32 operands only (rowlin2.hip).
+template <int MP>
+int try_forward_stats2_mp(const long *n, const int *k, int o, const float *const *x, const float *const *w, const float *const *bias, float *const *y,
+                          float *const *partial, hipStream_t s) {
+    if (o < 16 || (o & 15)) return 0;
+    FwdArgs2 q;
+    int nb[2], gy[2];
+    bool group[2];
+    for (int i = 0; i < 2; ++i) {
+        if (n[i] < 1 || !aligned16(x[i]) || !aligned16(w[i]) || !aligned16(y[i]) || !partial[i]) return 0;
+        const int nob = fwd_nob1(k[i], o, true, false);
+        if (!nob) return 0;
+        FwdArgs &a = q.a[i];
+        a.N = n[i]; a.O = o; a.ldx = k[i]; a.ldy = o; a.scale = a.shift = nullptr; a.relu = 0; a.accumulate = 0; a.partial = partial[i];
+        a.roww = nullptr; a.rws = 0; a.bx = nullptr; a.ldb = 0; a.bcoef = nullptr; a.brelu = 0; a.ho_gran = nullptr; a.ho_sync = nullptr;
+        a.wso = k[i]; a.wsk = 1;
+        for (int t = 0; t < 3; ++t) { a.X[t] = t ? nullptr : x[i]; a.W[t] = t ? nullptr : w[i]; a.bias[t] = t ? nullptr : bias[i]; a.Y[t] = t ? nullptr : y[i]; }
+        const int blocks = o / 16;
+        q.gx[i] = (unsigned)fwd_grid_rows(n[i], blocks / nob, false);
+        group[i] = k[i] >= 128 && group_form_wanted(a, k[i], blocks);
+        nb[i] = group[i] ? GROUP_GN : nob;
+        gy[i] = blocks / nb[i];
+    }
+    q.split = q.gx[0] * (unsigned)gy[0];
+    const unsigned total = q.split + q.gx[1] * (unsigned)gy[1];
+#define PDF_RL2S(K0_, NB0_, G0_, K1_, NB1_, G1_) \
+    if (k[0] == K0_ && nb[0] == NB0_ && group[0] == G0_ && k[1] == K1_ && nb[1] == NB1_ && group[1] == G1_) \
+        return launch_fwd_stats2<K0_, NB0_, G0_, K1_, NB1_, G1_, MP>(q, total, s) ? 1 : 0
+    PDF_RL2S(32, 2, false, 64, 1, false);
+    PDF_RL2S(64, 4, false, 128, GROUP_GN, true);
+    PDF_RL2S(128, GROUP_GN, true, 256, GROUP_GN, true);
+    PDF_RL2S(256, GROUP_GN, true, 512, GROUP_GN, true);
+    PDF_RL2S(512, GROUP_GN, true, 512, GROUP_GN, true);
+#undef PDF_RL2S
+    return 0;
+}
+
+// Arguments, grid and reduction of one k_wg launch over gradients that share the layer input; false: the shape or an alignment is not covered.
+struct WgSetup { WArgs a; RArgs r; dim3 grid; int vw; bool any_bias; };
+static bool wgrad_setup(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale, const float *shift,
+                        int relu, float *const *dw, float *const *db, float *ws, const float *roww, long rws, WgSetup &u) {
+    if (ng < 1 || ng > 3 || !ws) return false;
     const WgPlan p = wg_plan(n, k, o, ng);
     const int vw = p.vw;
-    if (!vw) return 0;
-    if ((ldg % vw) || (ldx % vw) || !aligned16(x)) return 0;
-    if (scale && (!aligned16(scale) || !aligned16(shift))) return 0;
-    for (int i = 0; i < ng; ++i) if (!aligned16(g[i])) return 0;
-    WArgs a;
+    if (!vw) return false;
+    if ((ldg % vw) || (ldx % vw) || !aligned16(x)) return false;
+    if (scale && (!aligned16(scale) || !aligned16(shift))) return false;
+    for (int i = 0; i < ng; ++i) if (!aligned16(g[i])) return false;
+    WArgs &a = u.a;
     a.N = n; a.K = k; a.O = o; a.ldg = ldg; a.X = x; a.ldx = ldx; a.scale = scale; a.shift = shift; a.relu = relu; a.roww = roww; a.rws = rws;
     a.per_z = 0;
-    bool any_bias = false;
+    u.any_bias = false;
     for (int i = 0; i < WG_MAXG; ++i) {
         a.G[i] = i < ng ? g[i] : nullptr; a.dW[i] = i < ng ? dw[i] : nullptr; a.db[i] = (db && i < ng) ? db[i] : nullptr;
         a.Xz[i] = nullptr; a.scalez[i] = a.shiftz[i] = nullptr; a.reluz[i] = 0;
-        any_bias = any_bias || a.db[i] != nullptr;
+        u.any_bias = u.any_bias || a.db[i] != nullptr;
     }
     const int b = p.b;
     a.rows_per_block = p.rows_per_block;
     a.slab = ws;
     a.bslab = ws + (size_t)p.nblk * p.split * b * b;
-    const dim3 grid((unsigned)p.split, (unsigned)((o / b) * (k / b)), (unsigned)ng);
+    u.vw = vw;
+    u.grid = dim3((unsigned)p.split, (unsigned)((o / b) * (k / b)), (unsigned)ng);
+    RArgs &r = u.r;
+    r.slab = a.slab; r.bslab = a.bslab; r.B = b; r.tiles_k = k / b; r.tiles = (o / b) * (k / b); r.otiles = o / b; r.split = (int)p.split; r.K = k; r.O = o;
+    for (int i = 0; i < WG_MAXG; ++i) { r.dW[i] = a.dW[i]; r.db[i] = a.db[i]; }
+    return true;
+}
+
+template <int MP>
+int try_wgrad_mp(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
+                 const float *shift, int relu, float *const *dw, float *const *db, float *ws, hipStream_t s, const float *roww, long rws,
+                 RArgs *defer) {   // defer: the slab reduction is not launched, its arguments are handed back (launch_slab_reduce2)
+    WgSetup u;
+    if (!wgrad_setup(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, roww, rws, u)) return 0;
+    const WArgs &a = u.a;
+    const dim3 grid = u.grid;
 #define PDF_WG(VW_) do { \
         if (roww) { if (scale) k_wg<VW_, true, true, MP><<<grid, 256, 0, s>>>(a); else k_wg<VW_, false, true, MP><<<grid, 256, 0, s>>>(a); } \
         else      { if (scale) k_wg<VW_, true, false, MP><<<grid, 256, 0, s>>>(a); else k_wg<VW_, false, false, MP><<<grid, 256, 0, s>>>(a); } } while (0)
-    if (vw == 4) PDF_WG(4); else PDF_WG(2);
+    if (u.vw == 4) PDF_WG(4); else PDF_WG(2);
 #undef PDF_WG
-    RArgs r;
-    r.slab = a.slab; r.bslab = a.bslab; r.B = b; r.tiles_k = k / b; r.tiles = (o / b) * (k / b); r.otiles = o / b; r.split = (int)p.split; r.K = k; r.O = o;
-    for (int i = 0; i < WG_MAXG; ++i) { r.dW[i] = a.dW[i]; r.db[i] = a.db[i]; }
-    if (defer) *defer = r;
-    else launch_slab_reduce(r, ng, any_bias, s);
+    if (defer) *defer = u.r;
+    else launch_slab_reduce(u.r, ng, u.any_bias, s);
+    return 1;
+}
+
+// Two single weight gradients dW_i (o_i, k_i) = G_i^T X_i (no prologue, own workspace each) whose slab reductions the caller launches
+// (r[i]: launch_slab_reduce2).  pair: the two products as ONE launch (k_wg2) where both take the same vector width -- the workgroups of the
+// problem with more rows per workgroup first; otherwise one launch each, as try_wgrad_mp issues them.  Either way every workgroup runs
+// wg_block over the grid of its own problem: the same slabs.  Returns 2 for one launch, 1 for two; 0: a shape or an alignment is not covered,
+// nothing was launched.
+template <int MP>
+int try_wgrad_pair_mp(const long *n, const int *k, const int *o, const float *const *g, const float *const *x, float *const *dw, float *const *db,
+                      float *const *ws, bool pair, hipStream_t s, RArgs *r) {
+    WgSetup u[2];
+    for (int i = 0; i < 2; ++i)
+        if (!wgrad_setup(n[i], k[i], o[i], 1, &g[i], o[i], x[i], k[i], nullptr, nullptr, 0, &dw[i], &db[i], ws[i], nullptr, 0, u[i])) return 0;
+    r[0] = u[0].r; r[1] = u[1].r;
+    if constexpr (MP == 0) {   // (the paired kernel is built for fp32 operands only: reduced-precision products take one launch each)
+        if (pair && u[0].vw == u[1].vw) {
+            const int first = u[1].a.rows_per_block > u[0].a.rows_per_block ? 1 : 0;
+            WArgs2 q;
+            for (int j = 0; j < 2; ++j) { const WgSetup &v = u[j ? 1 - first : first]; q.a[j] = v.a; q.gx[j] = v.grid.x; q.gy[j] = v.grid.y; }
+            q.split = q.gx[0] * q.gy[0];
+            const unsigned total = q.split + q.gx[1] * q.gy[1];
+            if (u[0].vw == 4) k_wg2<4, 0><<<total, 256, 0, s>>>(q); else k_wg2<2, 0><<<total, 256, 0, s>>>(q);
+            return 2;
+        }
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (u[i].vw == 4) k_wg<4, false, false, MP><<<u[i].grid, 256, 0, s>>>(u[i].a); else k_wg<2, false, false, MP><<<u[i].grid, 256, 0, s>>>(u[i].a);
+    }
     return 1;
 }
 

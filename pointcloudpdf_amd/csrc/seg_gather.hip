@@ -62,12 +62,13 @@ template <> __device__ __forceinline__ float zero<1>() { return 0.f; }
 
 // out[v, :] = scale * sum over the segment of src[e, :]          (src rows are indexed by the entry id itself)
 // (sv = source row stride in units of T: rows wider than the c channels that are summed, e.g. the (3 + c)-float rows of grouping(with_xyz))
+// (block: the workgroup's id in the grid of ITS problem -- blockIdx.x, or the id inside one half of k_seg_layer_pair)
 template <int V>
-__global__ __launch_bounds__(TB) void k_seg_rows(unsigned total, FastDiv cvd, unsigned sv, const typename Vec<V>::T *__restrict__ src,
-                                                 const int *__restrict__ inv_off, const int *__restrict__ inv_entry, int entry_base,
-                                                 float scale, typename Vec<V>::T *__restrict__ out) {
+__device__ __forceinline__ void seg_rows_block(unsigned block, unsigned total, FastDiv cvd, unsigned sv, const typename Vec<V>::T *__restrict__ src,
+                                               const int *__restrict__ inv_off, const int *__restrict__ inv_entry, int entry_base,
+                                               float scale, typename Vec<V>::T *__restrict__ out) {
     using T = typename Vec<V>::T;
-    const unsigned gid = blockIdx.x * TB + threadIdx.x;
+    const unsigned gid = block * TB + threadIdx.x;
     if (gid >= total) return;
     const unsigned v = fdiv(gid, cvd), p = gid - v * cvd.d, cv = cvd.d;
     int t = inv_off[v];
@@ -87,6 +88,12 @@ __global__ __launch_bounds__(TB) void k_seg_rows(unsigned total, FastDiv cvd, un
     }
     add_acc(a0, a1);
     out[(size_t)v * cv + p] = scaled(a0, scale);
+}
+template <int V>
+__global__ __launch_bounds__(TB) void k_seg_rows(unsigned total, FastDiv cvd, unsigned sv, const typename Vec<V>::T *__restrict__ src,
+                                                 const int *__restrict__ inv_off, const int *__restrict__ inv_entry, int entry_base,
+                                                 float scale, typename Vec<V>::T *__restrict__ out) {
+    seg_rows_block<V>(blockIdx.x, total, cvd, sv, src, inv_off, inv_entry, entry_base, scale, out);
 }
 
 // Both sums of a SELF table's backward in one walk (round 4; subtraction: d input1 = own-row sums, d input2 = - inverse-segment sums):
@@ -132,13 +139,14 @@ __global__ __launch_bounds__(TB) void k_seg_rows_own(unsigned total, FastDiv cvd
 //   aggregation grad_input (w = attention weights), fused layer g_xv (src = g_out, w = softmax weights), interpolation (w_c = 1)
 // `order` (nullable): visiting order of the DESTINATION rows (their Morton order): neighbouring destinations are gathered by the same
 // source rows, which then hit the L2 of the XCD that owns this stretch of the order (pdf_xcd_chunked_block).
+// (block, nblocks: the workgroup's id in the grid of ITS problem and that grid's size, as seg_rows_block)
 template <int V, bool WVEC>
-__global__ __launch_bounds__(TB) void k_seg_weighted(unsigned total, FastDiv cvd, FastDiv nsd, int w_c, const typename Vec<V>::T *__restrict__ src,
-                                                     const float *__restrict__ w, const int *__restrict__ inv_off,
-                                                     const int *__restrict__ inv_entry, int entry_base, const int *__restrict__ order,
-                                                     typename Vec<V>::T *__restrict__ out) {
+__device__ __forceinline__ void seg_weighted_block(unsigned block, unsigned nblocks, unsigned total, FastDiv cvd, FastDiv nsd, int w_c,
+                                                   const typename Vec<V>::T *__restrict__ src, const float *__restrict__ w,
+                                                   const int *__restrict__ inv_off, const int *__restrict__ inv_entry, int entry_base,
+                                                   const int *__restrict__ order, typename Vec<V>::T *__restrict__ out) {
     using T = typename Vec<V>::T;
-    const unsigned gid = pdf_xcd_chunked_block(blockIdx.x, gridDim.x) * TB + threadIdx.x;
+    const unsigned gid = pdf_xcd_chunked_block(block, nblocks) * TB + threadIdx.x;
     if (gid >= total) return;
     const unsigned sv = fdiv(gid, cvd), p = gid - sv * cvd.d, cv = cvd.d, v = order ? (unsigned)order[sv] : sv;
     const unsigned wo = (p * V) % (unsigned)w_c;   // first weight column of this piece (V consecutive channels; WVEC: w_c % 4 == 0)
@@ -169,6 +177,32 @@ __global__ __launch_bounds__(TB) void k_seg_weighted(unsigned total, FastDiv cvd
     }
     add_acc(a0, a1);
     out[(size_t)v * cv + p] = a0;
+}
+template <int V, bool WVEC>
+__global__ __launch_bounds__(TB) void k_seg_weighted(unsigned total, FastDiv cvd, FastDiv nsd, int w_c, const typename Vec<V>::T *__restrict__ src,
+                                                     const float *__restrict__ w, const int *__restrict__ inv_off,
+                                                     const int *__restrict__ inv_entry, int entry_base, const int *__restrict__ order,
+                                                     typename Vec<V>::T *__restrict__ out) {
+    seg_weighted_block<V, WVEC>(blockIdx.x, gridDim.x, total, cvd, nsd, w_c, src, w, inv_off, inv_entry, entry_base, order, out);
+}
+
+// The two inverse-table gathers of the fused PointTransformerLayer's backward over ONE table in one launch: g_xv (seg_weighted_block<4, true>:
+// src = g_out, w = softmax weights) on the first `nblocks` workgroups -- their hardware ids are their own, so the XCD-chunked visiting order
+// lands as in the single launch -- and g_xk (seg_rows_block<4>: src = the g_r rows) on the next `nblocks`.  Both problems have n rows of c
+// channels, hence one `total` and one grid size; neither reads what the other writes.
+struct SegLayerPair {
+    unsigned total, nblocks;
+    FastDiv cvd, nsd;
+    int w_c, entry_base;
+    const int *inv_off, *inv_entry, *order;
+    const float4 *wsrc; const float *w; float4 *wout;   // g_xv
+    const float4 *rsrc; unsigned rsv; float4 *rout;     // g_xk
+};
+__global__ __launch_bounds__(TB) void k_seg_layer_pair(SegLayerPair q) {
+    if (blockIdx.x < q.nblocks)
+        seg_weighted_block<4, true>(blockIdx.x, q.nblocks, q.total, q.cvd, q.nsd, q.w_c, q.wsrc, q.w, q.inv_off, q.inv_entry, q.entry_base, q.order, q.wout);
+    else
+        seg_rows_block<4>(blockIdx.x - q.nblocks, q.total, q.cvd, q.rsv, q.rsrc, q.inv_off, q.inv_entry, q.entry_base, 1.0f, q.rout);
 }
 
 // The fused PointTransformerLayer's reduced-precision variant keeps its g_r rows / softmax weights as bfloat16 (fp32 sums here).
@@ -308,5 +342,27 @@ extern "C" int pdf_seg_sum_weighted_x(long n, int c, int nsample, int w_c, const
     sg::k_seg_weighted_bfw<<<(unsigned)((total + sg::TB - 1) / sg::TB), sg::TB, 0, static_cast<hipStream_t>(stream)>>>(
         (unsigned)total, sg::mk_fastdiv(c / 4), sg::mk_fastdiv(nsample), w_c, reinterpret_cast<const float4 *>(src),
         reinterpret_cast<const unsigned short *>(w), inv_off, inv_entry, entry_base, reinterpret_cast<float4 *>(out));
+    return pdf_launch_status();
+}
+
+// g_xv (n, c) = pdf_seg_sum_weighted_ordered(src = gout, w (n * nsample, w_c), order) and g_xk (n, c) = pdf_seg_sum_rows(src = gr, scale 1) over
+// one inverse table as ONE launch (sg::k_seg_layer_pair): the bits of the two calls.  fp32 rows only; PDF_ERR_UNSUPPORTED, before any launch,
+// for what the two vector kernels do not cover (the caller then issues the two calls).
+int pdf_seg_layer_pair(long n, int c, int nsample, int w_c, const float *gout, const float *w, const float *gr, const int *inv_off, const int *inv_entry,
+                       int entry_base, const int *order, float *gxv, float *gxk, void *stream) {
+    if (n < 1 || c < 1 || nsample < 1 || w_c < 1 || !gout || !w || !gr || !inv_off || !inv_entry || !gxv || !gxk) return PDF_ERR_BAD_ARG;
+    if (c % 4 || w_c % 4 || c % w_c) return PDF_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(gout) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(gr) | reinterpret_cast<uintptr_t>(gxv) |
+         reinterpret_cast<uintptr_t>(gxk)) & 15)
+        return PDF_ERR_UNSUPPORTED;
+    const long total = n * (c / 4);
+    if (total >= (1L << 31)) return PDF_ERR_UNSUPPORTED;
+    sg::SegLayerPair q;
+    q.total = (unsigned)total; q.nblocks = (unsigned)((total + sg::TB - 1) / sg::TB);
+    q.cvd = sg::mk_fastdiv(c / 4); q.nsd = sg::mk_fastdiv(nsample); q.w_c = w_c; q.entry_base = entry_base;
+    q.inv_off = inv_off; q.inv_entry = inv_entry; q.order = order;
+    q.wsrc = reinterpret_cast<const float4 *>(gout); q.w = w; q.wout = reinterpret_cast<float4 *>(gxv);
+    q.rsrc = reinterpret_cast<const float4 *>(gr); q.rsv = (unsigned)(c / 4); q.rout = reinterpret_cast<float4 *>(gxk);
+    sg::k_seg_layer_pair<<<2 * q.nblocks, sg::TB, 0, static_cast<hipStream_t>(stream)>>>(q);
     return pdf_launch_status();
 }
