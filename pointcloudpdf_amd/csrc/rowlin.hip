@@ -10,7 +10,7 @@
 // N ~ 10^5 rows with 3..512 channels: HBM-bound (read X once per 64 output columns, write Y once); MFMA keeps the ~0.4 MFLOP/pt
 // off the VALU.  Shapes are arbitrary (edges are zero-padded in LDS), X / Y / G carry a row stride.
 #include "pdfops_common.h"
-#include <cstdlib>
+#include "rowlin2.h"   // the streaming kernels (rl2): cover the channel widths of the Bottleneck; the tiled kernels below take every other shape
 
 namespace rl {
 
@@ -187,49 +187,29 @@ __global__ __launch_bounds__(256) void k_wgrad(WArgs a) {
 
 }  // namespace rl
 
-// streaming kernels (rowlin2.hip): cover the channel widths of the Bottleneck; the tiled kernels above take every other shape
-namespace rl2 {
-int try_forward(long n, int k, int o, int nin, int nout, const float *const *x, long ldx, const float *const *w, int transpose_w,
-                const float *const *bias, const float *scale, const float *shift, int relu, float *const *y, long ldy,
-                int accumulate, float *partial, int mma, hipStream_t s, const float *roww = nullptr, long rws = 0, const float *bx = nullptr,
-                long ldb = 0, const float *bcoef = nullptr, int brelu = 0, int *partial_rows = nullptr, long ldw = 0, void *handoff = nullptr);
-long stats_rows_floats(long n, int o);
-long wgrad_ws_floats(long n, int k, int o, int ng);
-constexpr int WG_MAXG = 5;   // (as in rowlin2_impl.h)
-struct RArgs {
-    const float *slab, *bslab;
-    float *dW[WG_MAXG], *db[WG_MAXG];
-    int B, tiles_k, tiles, otiles, split, K, O;
-};
-int try_wgrad(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
-              const float *shift, int relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s, const float *roww = nullptr, long rws = 0,
-              RArgs *defer = nullptr);   // defer: the slab reduction is not launched, its arguments are handed back
-void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias1, hipStream_t s);
-int try_wgrad_group(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx, const float *const *scale,
-                    const float *const *shift, const int *relu, float *const *dw, float *const *db, float *ws, int mma, hipStream_t s);
-void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s);
-int try_forward2(const long *n, int k, const int *o, const float *const *x, const float *const *w, int transpose_w, float *const *y, int mma, hipStream_t s);
-int try_forward_stats2(const long *n, const int *k, int o, const float *const *x, const float *const *w, const float *const *bias, float *const *y,
-                       float *const *partial, int mma, hipStream_t s);
-int try_wgrad_pair(const long *n, const int *k, const int *o, const float *const *g, const float *const *x, float *const *dw, float *const *db,
-                   float *const *ws, bool pair, int mma, hipStream_t s, RArgs *r);   // r[2]: the two slab reductions, left to the caller
-int stats_rows(long n);
-}  // namespace rl2
-
-// split of the tiled weight-gradient kernel (shapes outside the streaming kernels)
-static inline void tiled_wg_plan(long n, int k, int o, int *blocks_oc, long *split, long *rows_per_block) {
-    *blocks_oc = ((o + 31) / 32) * ((k + 31) / 32);
-    long sp = (2048 + *blocks_oc - 1) / *blocks_oc;           // ~2048 workgroups in flight
+// Split and workspace of the tiled weight-gradient kernel (shapes outside the streaming kernels): ONE plan, from which
+// pdf_rowlin_wgrad_ws_floats takes the size and pdf_rowlin_wgrad the grid and the pointers (offsets and `floats` in floats from ws).
+// k_wgrad writes ONE slab per workgroup (since round 6; before, one per wave).  The size handed out still carries the per-wave factor 4:
+// dense.py packs these workspaces into shared scratch buffers, so a smaller size moves every address behind them -- a change of its own
+// (DESIGN section 10).  The surplus is never touched.
+constexpr int TILED_WS_SURPLUS = 4;
+struct TiledWgPlan { int blocks_oc, otiles; long split, rows_per_block, slab, bslab, floats; };
+static inline TiledWgPlan tiled_wg_plan(long n, int k, int o) {
+    TiledWgPlan p{};
+    p.otiles = (o + 31) / 32;
+    p.blocks_oc = p.otiles * ((k + 31) / 32);
+    long sp = (2048 + p.blocks_oc - 1) / p.blocks_oc;         // ~2048 workgroups in flight
     const long max_split = (n + 255) / 256;                   // at least 256 rows per workgroup
     if (sp > max_split) sp = max_split;
     if (sp < 1) sp = 1;
-    *rows_per_block = ((n + sp - 1) / sp + 31) / 32 * 32;
-    *split = (n + *rows_per_block - 1) / *rows_per_block;
+    p.rows_per_block = ((n + sp - 1) / sp + 31) / 32 * 32;
+    p.split = (n + p.rows_per_block - 1) / p.rows_per_block;
+    p.bslab = (long)p.blocks_oc * p.split * 1024;             // slab [blocks_oc][split][32 * 32] at 0, then bslab [otiles][split][32]
+    p.floats = TILED_WS_SURPLUS * (p.bslab + (long)p.otiles * p.split * 32);
+    return p;
 }
 
-static inline bool rowlin_streams(int k, int o) {
-    return (k == 32 || k == 64 || k == 128 || k == 256 || k == 512) && o % 16 == 0 && getenv("PDFOPS_ROWLIN_TILED") == nullptr;
-}
+static inline bool rowlin_streams(int k, int o) { return (k == 32 || k == 64 || k == 128 || k == 256 || k == 512) && o % 16 == 0; }
 
 int pdf_rowlin_streams(int k, int o) { return rowlin_streams(k, o) ? 1 : 0; }
 
@@ -241,17 +221,31 @@ extern "C" long pdf_rowlin_partial_floats(long n, int o) {   // rows of either k
     return (a > b ? a : b) + (long)PDF_HO_FLOATS;
 }
 
+// What every forward problem has (one input, one output); the call sites add what they use by name.
+static rl2::Forward forward1(long n, int k, int o, const float *x, long ldx, const float *w, int transpose_w, float *y, long ldy) {
+    rl2::Forward p;
+    p.n = n; p.k = k; p.o = o; p.x[0] = x; p.ldx = ldx; p.w[0] = w; p.transpose_w = transpose_w; p.y[0] = y; p.ldy = ldy;
+    return p;
+}
+// What every weight-gradient problem has; the call sites add gradients, inputs and outputs by name.
+static rl2::Wgrad wgrad_shape(long n, int k, int o, long ldg, long ldx, float *ws) {
+    rl2::Wgrad p;
+    p.n = n; p.k = k; p.o = o; p.ldg = ldg; p.ldx = ldx; p.ws = ws;
+    return p;
+}
+
 // Y (n, o; row stride ldy) (+)= f(X (n, k; row stride ldx)) * Wt + bias.  transpose_w = 0: W is (o, k) row-major (forward);
 // 1: W is (k, o) row-major, i.e. the layer's own (out, in) weight used for the input gradient dX = G W.
 extern "C" int pdf_rowlin_forward(long n, int k, int o, const float *x, long ldx, const float *w, int transpose_w,
                                   const float *bias, const float *scale, const float *shift, int relu, float *y, long ldy,
                                   int accumulate, float *partial, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || k < 1 || o < 1 || !x || !w || !y || ldx < k || ldy < o) return PDF_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (rowlin_streams(k, o)) {
-        if (rl2::try_forward(n, k, o, 1, 1, &x, ldx, &w, transpose_w, &bias, scale, shift, relu, &y, ldy, accumulate, partial,
-                             mma_input, static_cast<hipStream_t>(stream)))
-            return pdf_launch_status();
+        rl2::Forward p = forward1(n, k, o, x, ldx, w, transpose_w, y, ldy);
+        p.bias[0] = bias; p.scale = scale; p.shift = shift; p.relu = relu; p.accumulate = accumulate; p.partial = partial;
+        if (rl2::try_forward(p, mma_input, s)) return pdf_launch_status();
         if (partial) return PDF_ERR_BAD_ARG;  // statistics layout is tied to the streaming kernel for these shapes (needs 16-byte alignment)
     }
     // k = 1024 (the TransitionUp head's Linear(2 * 512, 512), point_transformer_seg.py:131-136) as ONE launch of the streaming kernel over
@@ -259,18 +253,16 @@ extern "C" int pdf_rowlin_forward(long n, int k, int o, const float *x, long ldx
     // the association of a single 1024-long dot product).  The tiled kernel below walks such a k serially in a handful of workgroups:
     // 274 us at 780 x 1024 -> 512 against ~20 us.
     if (!transpose_w && !partial && !scale && k == 1024 && rowlin_streams(512, o) && !(ldx & 3) && !(ldy & 3)) {
-        const float *xs[2] = {x, x + 512}, *ws[2] = {w, w + 512};
-        if (rl2::try_forward(n, 512, o, 2, 1, xs, ldx, ws, 0, &bias, nullptr, nullptr, 0, &y, ldy, accumulate, nullptr, mma_input, static_cast<hipStream_t>(stream),
-                             nullptr, 0, nullptr, 0, nullptr, 0, nullptr, k))
-            return pdf_launch_status();
+        rl2::Forward p = forward1(n, 512, o, x, ldx, w, 0, y, ldy);
+        p.nin = 2; p.x[1] = x + 512; p.w[1] = w + 512; p.ldw = k; p.bias[0] = bias; p.accumulate = accumulate;
+        if (rl2::try_forward(p, mma_input, s)) return pdf_launch_status();
     }
-    rl::FwdArgs a;
+    rl::FwdArgs a{};
     a.N = n; a.K = k; a.O = o; a.X = x; a.ldx = ldx; a.W = w;
     a.wso = transpose_w ? 1 : k; a.wsk = transpose_w ? o : 1;
     a.bias = bias; a.scale = scale; a.shift = shift; a.relu = relu; a.Y = y; a.ldy = ldy; a.accumulate = accumulate;
     a.partial = partial;
     const dim3 grid((unsigned)((n + rl::BM - 1) / rl::BM), (unsigned)((o + rl::BN - 1) / rl::BN));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const bool pre = scale != nullptr, stats = partial != nullptr;
     if (pre && stats) rl::k_rowlin<true, true><<<grid, 256, 0, s>>>(a);
     else if (pre) rl::k_rowlin<true, false><<<grid, 256, 0, s>>>(a);
@@ -283,9 +275,7 @@ extern "C" int pdf_rowlin_forward(long n, int k, int o, const float *x, long ldx
 // launch sums the slabs in a fixed order -- no float atomics, bit-reproducible gradients (ng = number of gradients of a _multi call).
 extern "C" long pdf_rowlin_wgrad_ws_floats(long n, int k, int o, int ng) {
     if (n < 1 || k < 1 || o < 1 || ng < 1) return 0;
-    int blocks_oc; long split, rpb;
-    tiled_wg_plan(n, k, o, &blocks_oc, &split, &rpb);
-    const long tiled = (long)blocks_oc * split * 4 * 1024 + (long)((o + 31) / 32) * split * 4 * 32;   // (_multi falls back to ng single calls)
+    const long tiled = tiled_wg_plan(n, k, o).floats;   // (_multi falls back to ng single calls)
     const long streaming = rowlin_streams(k, o) ? rl2::wgrad_ws_floats(n, k, o, ng) : 0;
     return tiled > streaming ? tiled : streaming;
 }
@@ -299,14 +289,14 @@ extern "C" int pdf_bn_coef_from_partial(const float *partial, int rows, long n, 
 extern "C" int pdf_rowlin_forward_bn(long n, int k, int o, const float *x, long ldx, const float *w, const float *bias, const float *scale,
                                      const float *shift, int relu, float *y, long ldy, float *partial, const float *gamma, const float *beta,
                                      float *running_mean, float *running_var, float eps, float momentum, float *coef, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || k < 1 || o < 1 || !x || !w || !y || !partial || !gamma || !beta || !coef || ldx < k || ldy < o) return PDF_ERR_BAD_ARG;
     if (rowlin_streams(k, o)) {
+        rl2::Forward p = forward1(n, k, o, x, ldx, w, 0, y, ldy);
+        p.bias[0] = bias; p.scale = scale; p.shift = shift; p.relu = relu; p.partial = partial;
         int rows = 0;
-        if (rl2::try_forward(n, k, o, 1, 1, &x, ldx, &w, 0, &bias, scale, shift, relu, &y, ldy, 0, partial, mma_input, static_cast<hipStream_t>(stream),
-                             nullptr, 0, nullptr, 0, nullptr, 0, &rows)) {
+        if (rl2::try_forward(p, mma_input, static_cast<hipStream_t>(stream), &rows))
             return pdf_bn_coef_from_partial(partial, rows, n, o, gamma, beta, running_mean, running_var, eps, momentum, coef, stream);
-        }
     }
     const int rc = pdf_rowlin_forward(n, k, o, x, ldx, w, 0, bias, scale, shift, relu, y, ldy, 0, partial, mma_input, stream);
     if (rc) return rc;
@@ -320,34 +310,37 @@ int pdf_rowlin_forward_stats_ho(long n, int k, int o, const float *x, long ldx, 
                                 const float *shift, int relu, float *y, long ldy, float *rows_out, void *handoff, int *rows, int mma_input,
                                 void *stream) {
     if (!rowlin_streams(k, o)) return PDF_ERR_UNSUPPORTED;
-    if (!rl2::try_forward(n, k, o, 1, 1, &x, ldx, &w, 0, &bias, scale, shift, relu, &y, ldy, 0, rows_out, mma_input, static_cast<hipStream_t>(stream),
-                          nullptr, 0, nullptr, 0, nullptr, 0, rows, 0, handoff))
-        return PDF_ERR_UNSUPPORTED;
+    rl2::Forward p = forward1(n, k, o, x, ldx, w, 0, y, ldy);
+    p.bias[0] = bias; p.scale = scale; p.shift = shift; p.relu = relu; p.partial = rows_out; p.handoff = handoff;
+    if (!rl2::try_forward(p, mma_input, static_cast<hipStream_t>(stream), rows)) return PDF_ERR_UNSUPPORTED;
     return pdf_launch_status();
 }
 
 // dW (o, k) = G^T f(X), db (o) = column sums of G (db may be null); both are WRITTEN.  ws: pdf_rowlin_wgrad_ws_floats(n, k, o, 1) floats.
 extern "C" int pdf_rowlin_wgrad(long n, int k, int o, const float *g, long ldg, const float *x, long ldx,
                                 const float *scale, const float *shift, int relu, float *dw, float *db, float *ws, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || k < 1 || o < 1 || !g || !x || !dw || !ws || ldg < o || ldx < k) return PDF_ERR_BAD_ARG;
-    if (rowlin_streams(k, o) && rl2::try_wgrad(n, k, o, 1, &g, ldg, x, ldx, scale, shift, relu, &dw, &db, ws, mma_input, static_cast<hipStream_t>(stream)))
-        return pdf_launch_status();
-    rl::WArgs a;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (rowlin_streams(k, o)) {
+        rl2::Wgrad p = wgrad_shape(n, k, o, ldg, ldx, ws);
+        p.g[0] = g; p.x = x; p.scale = scale; p.shift = shift; p.relu = relu; p.dw[0] = dw; p.db[0] = db;
+        if (rl2::try_wgrad(p, mma_input, s)) return pdf_launch_status();
+    }
+    const TiledWgPlan pl = tiled_wg_plan(n, k, o);
+    rl::WArgs a{};
     a.N = n; a.K = k; a.O = o; a.G = g; a.ldg = ldg; a.X = x; a.ldx = ldx; a.scale = scale; a.shift = shift; a.relu = relu;
     a.dW = dw; a.db = db;
-    int blocks_oc; long split;
-    tiled_wg_plan(n, k, o, &blocks_oc, &split, &a.rows_per_block);
-    a.slab = ws;
-    a.bslab = ws + (size_t)blocks_oc * split * 1024;
-    const dim3 grid((unsigned)split, (unsigned)blocks_oc);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    a.rows_per_block = pl.rows_per_block;
+    a.slab = ws + pl.slab;
+    a.bslab = ws + pl.bslab;
+    const dim3 grid((unsigned)pl.split, (unsigned)pl.blocks_oc);
     if (scale) rl::k_wgrad<true><<<grid, 256, 0, s>>>(a);
     else rl::k_wgrad<false><<<grid, 256, 0, s>>>(a);
-    rl2::RArgs r;
-    r.slab = a.slab; r.bslab = a.bslab; r.B = 32; r.tiles_k = (k + 31) / 32; r.tiles = blocks_oc; r.otiles = (o + 31) / 32; r.split = (int)split;
+    rl2::RArgs r{};
+    r.slab = a.slab; r.bslab = a.bslab; r.B = 32; r.tiles_k = (k + 31) / 32; r.tiles = pl.blocks_oc; r.otiles = pl.otiles; r.split = (int)pl.split;
     r.K = k; r.O = o;
-    r.dW[0] = dw; r.db[0] = db; r.dW[1] = r.dW[2] = nullptr; r.db[1] = r.db[2] = nullptr;
+    r.dW[0] = dw; r.db[0] = db;
     rl2::launch_slab_reduce(r, 1, db != nullptr, s);
     return pdf_launch_status();
 }
@@ -359,15 +352,18 @@ extern "C" int pdf_rowlin_wgrad(long n, int k, int o, const float *g, long ldg, 
 // 1 when the two products went out as one launch, 0 when as two.
 int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream, int *paired) {
     if (paired) *paired = 0;
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
+    rl2::Wgrad p[2];
     for (int i = 0; i < 2; ++i) {
         if (q.n[i] < 1 || q.k[i] < 1 || q.o[i] < 1 || !q.g[i] || !q.x[i] || !q.dw[i] || !q.ws[i]) return PDF_ERR_BAD_ARG;
         if (!rowlin_streams(q.k[i], q.o[i]) || (q.k[i] % 32) || (q.o[i] % 32)) return PDF_ERR_UNSUPPORTED;
         if ((reinterpret_cast<uintptr_t>(q.g[i]) | reinterpret_cast<uintptr_t>(q.x[i])) & 15) return PDF_ERR_UNSUPPORTED;
+        p[i] = wgrad_shape(q.n[i], q.k[i], q.o[i], q.o[i], q.k[i], q.ws[i]);
+        p[i].g[0] = q.g[i]; p[i].x = q.x[i]; p[i].dw[0] = q.dw[i]; p[i].db[0] = q.db[i];
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rl2::RArgs r[2];
-    const int took = rl2::try_wgrad_pair(q.n, q.k, q.o, q.g, q.x, q.dw, q.db, q.ws, pdf_pair_launches(), mma_input, s, r);
+    rl2::RArgs r[2] = {};
+    const int took = rl2::try_wgrad_pair(p, pdf_pair_launches(), mma_input, s, r);
     if (!took) return PDF_ERR_UNSUPPORTED;   // (not reached: the conditions of the setup are checked above)
     if (paired) *paired = took == 2;
     rl2::launch_slab_reduce2(r[0], q.db[0] != nullptr, r[1], q.db[1] != nullptr, s);
@@ -380,18 +376,23 @@ int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream, int *
 // way.  paired (nullable): receives 1 when the products went out as one launch, 0 when as two.
 int pdf_rowlin_forward_stats_pair(const PdfFwdStats2 &q, int mma_input, void *stream, int *paired) {
     if (paired) *paired = 0;
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (q.o < 1) return PDF_ERR_BAD_ARG;
     for (int i = 0; i < 2; ++i)
         if (q.n[i] < 1 || q.k[i] < 1 || !q.x[i] || !q.w[i] || !q.y[i] || !q.partial[i]) return PDF_ERR_BAD_ARG;
     for (int i = 0; i < 2; ++i)   // (what pdf_rowlin_forward refuses with statistics, before the first launch)
         if (rowlin_streams(q.k[i], q.o) && ((reinterpret_cast<uintptr_t>(q.x[i]) | reinterpret_cast<uintptr_t>(q.w[i]) | reinterpret_cast<uintptr_t>(q.y[i])) & 15))
             return PDF_ERR_BAD_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (pdf_pair_launches() && rowlin_streams(q.k[0], q.o) && rowlin_streams(q.k[1], q.o) &&
-        rl2::try_forward_stats2(q.n, q.k, q.o, q.x, q.w, q.bias, q.y, q.partial, mma_input, s)) {
-        if (paired) *paired = 1;
-        return pdf_launch_status();
+    if (pdf_pair_launches() && rowlin_streams(q.k[0], q.o) && rowlin_streams(q.k[1], q.o)) {
+        rl2::Forward p[2];
+        for (int i = 0; i < 2; ++i) {
+            p[i] = forward1(q.n[i], q.k[i], q.o, q.x[i], q.k[i], q.w[i], 0, q.y[i], q.o);
+            p[i].bias[0] = q.bias[i]; p[i].partial = q.partial[i];
+        }
+        if (rl2::try_forward_stats2(p, mma_input, static_cast<hipStream_t>(stream))) {
+            if (paired) *paired = 1;
+            return pdf_launch_status();
+        }
     }
     int rc = 0;
     for (int i = 0; i < 2 && rc == 0; ++i)
@@ -416,15 +417,17 @@ extern "C" int pdf_rowlin_forward_stats2(long n0, int k0, long n1, int k1, int o
 // paired (nullable): receives 1 when the products went out as one launch (fp32 operands, same slab width and form), 0 when as two.
 int pdf_rowlin_dgrad_pair(const PdfDgrad2 &q, int mma_input, void *stream, int *paired) {
     if (paired) *paired = 0;
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (q.o < 1) return PDF_ERR_BAD_ARG;
     for (int i = 0; i < 2; ++i)
         if (q.n[i] < 1 || q.k[i] < 1 || !q.g[i] || !q.w[i]) return PDF_ERR_BAD_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (q.gx[0] && q.gx[1] && pdf_pair_launches() && rowlin_streams(q.o, q.k[0]) && rowlin_streams(q.o, q.k[1]) &&
-        rl2::try_forward2(q.n, q.o, q.k, q.g, q.w, 1, q.gx, mma_input, s)) {
-        if (paired) *paired = 1;
-        return pdf_launch_status();
+    if (q.gx[0] && q.gx[1] && pdf_pair_launches() && rowlin_streams(q.o, q.k[0]) && rowlin_streams(q.o, q.k[1])) {
+        rl2::Forward p[2];   // (the product reduces over o and is k_i wide)
+        for (int i = 0; i < 2; ++i) p[i] = forward1(q.n[i], q.o, q.k[i], q.g[i], q.o, q.w[i], 1, q.gx[i], q.k[i]);
+        if (rl2::try_forward2(p, mma_input, static_cast<hipStream_t>(stream))) {
+            if (paired) *paired = 1;
+            return pdf_launch_status();
+        }
     }
     int rc = 0;
     for (int i = 0; i < 2 && rc == 0; ++i)
@@ -455,18 +458,24 @@ extern "C" int pdf_rowlin_wgrad2(long n0, int k0, int o0, long n1, int k1, int o
     return pdf_rowlin_wgrad2_paired(n0, k0, o0, n1, k1, o1, p, nullptr, mma_input, stream);
 }
 
-// Several Linear layers over the same rows in one launch (channel widths 32..256, see rowlin2.hip):
+// Several Linear layers over the same rows in one launch (channel widths 32..256, see rowlin2_impl.h):
 //   nin = 1, nout = 1..3 :  y[i] = f(x[0]) Wt[i] + bias[i]              (q, k, v projections from one read of x)
 //   nin = 1..3, nout = 1 :  y[0] (+)= sum_i x[i] Wt[i] (+ bias[0])      (input gradient of the three projections)
 // Shapes the streaming kernels do not cover are issued as single-layer launches.
 extern "C" int pdf_rowlin_multi(long n, int k, int o, int nin, int nout, const float *const *x, long ldx, const float *const *w,
                                 int transpose_w, const float *const *bias, const float *scale, const float *shift, int relu,
                                 float *const *y, long ldy, int accumulate, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || k < 1 || o < 1 || !x || !w || !y || nin < 1 || nout < 1 || nin > 3 || nout > 3 || (nin > 1 && nout > 1)) return PDF_ERR_BAD_ARG;
-    if (rowlin_streams(k, o) && rl2::try_forward(n, k, o, nin, nout, x, ldx, w, transpose_w, bias, scale, shift, relu, y, ldy, accumulate,
-                                                 nullptr, mma_input, static_cast<hipStream_t>(stream)))
-        return pdf_launch_status();
+    if (rowlin_streams(k, o)) {
+        rl2::Forward p = forward1(n, k, o, x[0], ldx, w[0], transpose_w, y[0], ldy);
+        p.nin = nin; p.nout = nout; p.scale = scale; p.shift = shift; p.relu = relu; p.accumulate = accumulate;
+        for (int i = 1; i < nin; ++i) p.x[i] = x[i];
+        for (int i = 1; i < (nin > 1 ? nin : nout); ++i) p.w[i] = w[i];
+        for (int i = 1; i < nout; ++i) p.y[i] = y[i];
+        for (int i = 0; bias && i < nout; ++i) p.bias[i] = bias[i];
+        if (rl2::try_forward(p, mma_input, static_cast<hipStream_t>(stream))) return pdf_launch_status();
+    }
     int rc = 0;
     if (nin == 1) {
         for (int i = 0; i < nout && rc == 0; ++i)
@@ -487,13 +496,14 @@ extern "C" int pdf_rowlin_multi(long n, int k, int o, int nin, int nout, const f
 extern "C" int pdf_rowlin_dgrad_bstats(long n, int k, int o, int nin, const float *const *x, long ldx, const float *const *w, float *y, long ldy,
                                        const float *bx, long ldb, const float *bcoef, int brelu, float *partial, int *partial_rows,
                                        int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || k < 1 || o < 1 || !x || !w || !y || nin < 1 || nin > 3 || !bx || !bcoef || !partial || !partial_rows) return PDF_ERR_BAD_ARG;
     if (!rowlin_streams(k, o)) return PDF_ERR_UNSUPPORTED;
-    float *ys[1] = {y};
-    if (!rl2::try_forward(n, k, o, nin, 1, x, ldx, w, 1, nullptr, nullptr, nullptr, 0, ys, ldy, 0, partial, mma_input, static_cast<hipStream_t>(stream),
-                          nullptr, 0, bx, ldb, bcoef, brelu, partial_rows))
-        return PDF_ERR_UNSUPPORTED;
+    rl2::Forward p = forward1(n, k, o, x[0], ldx, w[0], 1, y, ldy);
+    p.nin = nin;
+    for (int i = 1; i < nin; ++i) { p.x[i] = x[i]; p.w[i] = w[i]; }
+    p.partial = partial; p.bx = bx; p.ldb = ldb; p.bcoef = bcoef; p.brelu = brelu;
+    if (!rl2::try_forward(p, mma_input, static_cast<hipStream_t>(stream), partial_rows)) return PDF_ERR_UNSUPPORTED;
     return pdf_launch_status();
 }
 
@@ -502,10 +512,14 @@ extern "C" int pdf_rowlin_dgrad_bstats(long n, int k, int o, int nin, const floa
 extern "C" int pdf_rowlin_wgrad_multi(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx,
                                       const float *scale, const float *shift, int relu, float *const *dw, float *const *db,
                                       float *ws, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || k < 1 || o < 1 || ng < 1 || ng > 3 || !g || !x || !dw || !ws) return PDF_ERR_BAD_ARG;
-    if (rowlin_streams(k, o) && rl2::try_wgrad(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, mma_input, static_cast<hipStream_t>(stream)))
-        return pdf_launch_status();
+    if (rowlin_streams(k, o)) {
+        rl2::Wgrad p = wgrad_shape(n, k, o, ldg, ldx, ws);
+        p.ng = ng; p.x = x; p.scale = scale; p.shift = shift; p.relu = relu;
+        for (int i = 0; i < ng; ++i) { p.g[i] = g[i]; p.dw[i] = dw[i]; p.db[i] = db ? db[i] : nullptr; }
+        if (rl2::try_wgrad(p, mma_input, static_cast<hipStream_t>(stream))) return pdf_launch_status();
+    }
     int rc = 0;   // (stream order: the next call reuses the workspace after this call's reduction has read it)
     for (int i = 0; i < ng && rc == 0; ++i) rc = pdf_rowlin_wgrad(n, k, o, g[i], ldg, x, ldx, scale, shift, relu, dw[i], db ? db[i] : nullptr, ws, mma_input, stream);
     return rc;
@@ -518,11 +532,17 @@ extern "C" int pdf_rowlin_wgrad_multi(long n, int k, int o, int ng, const float 
 extern "C" int pdf_rowlin_wgrad_group(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx,
                                       const float *const *scale, const float *const *shift, const int *relu, float *const *dw,
                                       float *const *db, float *ws, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || k < 1 || o < 1 || ng < 1 || ng > rl2::WG_MAXG || !g || !x || !scale || !shift || !relu || !dw || !ws) return PDF_ERR_BAD_ARG;
     for (int i = 0; i < ng; ++i) if (!g[i] || !x[i] || !dw[i] || (scale[i] && !shift[i])) return PDF_ERR_BAD_ARG;
-    if (!rowlin_streams(k, o) || !rl2::try_wgrad_group(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, mma_input, static_cast<hipStream_t>(stream)))
-        return PDF_ERR_UNSUPPORTED;
+    if (!rowlin_streams(k, o)) return PDF_ERR_UNSUPPORTED;
+    rl2::Wgrad p = wgrad_shape(n, k, o, ldg, ldx, ws);
+    p.ng = ng; p.per_gradient = true;
+    for (int i = 0; i < ng; ++i) {
+        p.g[i] = g[i]; p.xz[i] = x[i]; p.scalez[i] = scale[i]; p.shiftz[i] = shift[i]; p.reluz[i] = relu[i];
+        p.dw[i] = dw[i]; p.db[i] = db ? db[i] : nullptr;
+    }
+    if (!rl2::try_wgrad(p, mma_input, static_cast<hipStream_t>(stream))) return PDF_ERR_UNSUPPORTED;
     return pdf_launch_status();
 }
 
@@ -530,20 +550,19 @@ extern "C" int pdf_rowlin_wgrad_group(long n, int k, int o, int ng, const float 
 // the input gradient cnt .* (x Q)): y = roww[n] * (x Wt) (+)= ..., dW += sum_n roww[n] g[n]^T x[n].  roww has element stride rws.
 extern "C" int pdf_rowlin_forward_roww(long n, int k, int o, const float *x, long ldx, const float *w, int transpose_w, float *y, long ldy,
                                        int accumulate, const float *roww, long rws, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || !x || !w || !y || !rowlin_streams(k, o)) return PDF_ERR_UNSUPPORTED;
-    const float *bias = nullptr;
-    if (!rl2::try_forward(n, k, o, 1, 1, &x, ldx, &w, transpose_w, &bias, nullptr, nullptr, 0, &y, ldy, accumulate, nullptr,
-                          mma_input, static_cast<hipStream_t>(stream), roww, rws))
-        return PDF_ERR_UNSUPPORTED;
+    rl2::Forward p = forward1(n, k, o, x, ldx, w, transpose_w, y, ldy);
+    p.accumulate = accumulate; p.roww = roww; p.rws = rws;
+    if (!rl2::try_forward(p, mma_input, static_cast<hipStream_t>(stream))) return PDF_ERR_UNSUPPORTED;
     return pdf_launch_status();
 }
 extern "C" int pdf_rowlin_wgrad_roww(long n, int k, int o, const float *g, long ldg, const float *x, long ldx, float *dw, const float *roww,
                                      long rws, float *ws, int mma_input, void *stream) {
-    if (mma_input < 0 || mma_input > 2) return PDF_ERR_BAD_ARG;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
     if (n < 1 || !g || !x || !dw || !ws || !rowlin_streams(k, o)) return PDF_ERR_UNSUPPORTED;
-    float *db = nullptr;
-    if (!rl2::try_wgrad(n, k, o, 1, &g, ldg, x, ldx, nullptr, nullptr, 0, &dw, &db, ws, mma_input, static_cast<hipStream_t>(stream), roww, rws))
-        return PDF_ERR_UNSUPPORTED;
+    rl2::Wgrad p = wgrad_shape(n, k, o, ldg, ldx, ws);
+    p.g[0] = g; p.x = x; p.dw[0] = dw; p.roww = roww; p.rws = rws;
+    if (!rl2::try_wgrad(p, mma_input, static_cast<hipStream_t>(stream))) return PDF_ERR_UNSUPPORTED;
     return pdf_launch_status();
 }

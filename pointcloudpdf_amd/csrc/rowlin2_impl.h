@@ -21,11 +21,15 @@
 //
 // fp32 in / fp32 accumulate (bit-equal to an fmaf chain): the reference computes these layers in fp32.
 //
-// This header is the implementation; it is compiled three times, once per input precision of the products (template parameter MP, see
-// Mma below): rowlin2.hip (MP = 0, fp32 operands -- plus the precision-independent helpers, RL2_MAIN_TU), rowlin2_f16.hip (MP = 1),
-// rowlin2_bf16.hip (MP = 2).  Each translation unit instantiates try_forward_mp<MP> / try_wgrad_mp<MP> explicitly.
+// Layout: rowlin2.h declares the host interface (the problem structs Forward / Wgrad, RArgs, the try_* prototypes) for rowlin.hip.  This
+// header is the implementation -- the kernels, then the host code that turns a described problem into kernel arguments and a launch:
+// fwd_args (the one place a FwdArgs is validated and filled), wg_plan + wg_setup (the one place WArgs / RArgs / grid are made, from the
+// plan that also sizes the workspace) and the try_*_mp<MP> templates.  It is compiled three times, once per input precision of the
+// products (template parameter MP, see Mma below): rowlin2.hip (MP = 0, fp32 operands -- plus the precision-independent helpers,
+// RL2_MAIN_TU, the paired products and the one dispatch on `mma_input`), rowlin2_f16.hip (MP = 1), rowlin2_bf16.hip (MP = 2).  Each
+// translation unit instantiates its try_forward_mp / try_wgrad_mp / try_wgrad_pair_mp<MP> explicitly, one line each.
 #pragma once
-#include "pdfops_common.h"
+#include "rowlin2.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -59,8 +63,6 @@ template <> struct Mma<2> {
     static __device__ __forceinline__ frag cvt(f32x4 v) { return __builtin_bit_cast(s16x4, __builtin_convertvector(v, b16x4)); }
     static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, acc, 0, 0, 0); }
 };
-
-long stats_rows_floats(long n, int o);
 
 struct FwdArgs {
     long N;
@@ -461,7 +463,6 @@ __global__ __launch_bounds__(256, (G0 || G1) ? 2 : 1) void k_fwd_stats2(FwdArgs2
     }
 }
 
-constexpr int WG_MAXG = 5;   // weight gradients of one launch (blockIdx.z): q / k / v of one input, or the five c x c products of a Bottleneck
 struct WArgs {
     long N;
     int K, O;
@@ -611,16 +612,7 @@ __global__ __launch_bounds__(256) void k_wg2(WArgs2 q) {
     wg_block<VW, false, false, MP>(q.a[i], b % gx, b / gx, 0u, gx, q.gy[i]);
 }
 
-// Sum of the `split` slabs of every dW block (and bias block) in a fixed order: lane l of an element adds slabs l, l + L, l + 2L, ...,
-// the L partial sums are combined in lane order.  grid = (ceil(B^2 / 64), tiles + bias tiles, ng), 64 L threads.  Works for the tiled
-// kernel of rowlin.hip as well (B = 32, edge blocks masked by O / K).
-struct RArgs {
-    const float *slab, *bslab;
-    float *dW[WG_MAXG], *db[WG_MAXG];
-    int B, tiles_k, tiles, otiles, split, K, O;
-};
-void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s);
-void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias1, hipStream_t s);
+// The slab reduction (RArgs and its order of summation: rowlin2.h).
 // One workgroup of the reduction: (bx, by, z) = its block id in the grid of ITS problem; lanes 64 L and above of a wider workgroup (the
 // two-problem launch, whose problems may differ in L) only take part in the barrier.
 template <int L, bool WIDE>
@@ -703,29 +695,28 @@ void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias
 }
 #endif
 
-// split of the row range for (n, k, o, ng): workgroups in flight vs rows per workgroup (shared by the launch and the workspace size)
-struct WgPlan { int vw, b, nblk; long split, rows_per_block; };
+// Split of the row range for (n, k, o, ng) -- workgroups in flight against rows per workgroup -- and the workspace that goes with it: ONE
+// plan, from which wgrad_ws_floats takes the size and wg_setup the grid and the pointers.  Offsets and `floats` in floats from ws.
+struct WgPlan { int vw, b, nblk; long split, rows_per_block, slab, bslab, floats; };
+constexpr int WG_BLOCKS = 512;   // workgroups aimed at (256 and 1024 measured no better over a step: profiles/r03_knobs_ab.txt)
 static WgPlan wg_plan(long n, int k, int o, int ng) {
-    WgPlan p;
+    WgPlan p{};
     p.vw = (k % 64 == 0 && o % 64 == 0) ? 4 : ((k % 32 == 0 && o % 32 == 0) ? 2 : 0);
     p.b = 16 * p.vw;
-    if (!p.vw) { p.nblk = 0; p.split = 0; p.rows_per_block = 0; return p; }
+    if (!p.vw) return p;
     p.nblk = (o / p.b) * (k / p.b) * ng;
-    static const int target = [] { const char *v = getenv("PDFOPS_WG_BLOCKS"); const int x = v ? atoi(v) : 0; return x > 0 ? x : 512; }();
-    long split = (target + p.nblk - 1) / p.nblk;       // workgroups in flight
+    long split = (WG_BLOCKS + p.nblk - 1) / p.nblk;    // workgroups in flight
     const long max_split = (n + 255) / 256;            // at least 256 rows (4 trips per wave) per workgroup
     if (split > max_split) split = max_split;
     if (split < 1) split = 1;
     p.rows_per_block = ((n + split - 1) / split + 63) / 64 * 64;
     p.split = (n + p.rows_per_block - 1) / p.rows_per_block;
+    p.bslab = (long)p.nblk * p.split * p.b * p.b;                      // slab [ng][blocks][split][b^2] at 0, then ...
+    p.floats = p.bslab + (long)ng * (o / p.b) * p.split * p.b;         // ... bslab [ng][o / b][split][b]
     return p;
 }
 #ifdef RL2_MAIN_TU
-long wgrad_ws_floats(long n, int k, int o, int ng) {
-    const WgPlan p = wg_plan(n, k, o, ng);
-    if (!p.vw) return 0;
-    return (long)p.nblk * p.split * p.b * p.b + (long)ng * (o / p.b) * p.split * p.b;
-}
+long wgrad_ws_floats(long n, int k, int o, int ng) { return wg_plan(n, k, o, ng).floats; }
 #endif
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -767,11 +758,11 @@ static bool launch_fwd_group(const FwdArgs &a, int blocks, int gx, hipStream_t s
     return pre ? launch_group_kernel<K, GN, NIN, true, 0, MP>(a, grid, s) : launch_group_kernel<K, GN, NIN, false, 0, MP>(a, grid, s);
 }
 
-// Row blocks of a launch with `nslabs` column slabs (launch_fwd below: what `capped` is for, and the measurements behind 512).
+// Row blocks of a launch with `nslabs` column slabs (launch_fwd below: what `capped` is for, and the measurements behind FWD_BLOCKS).
+constexpr int FWD_BLOCKS = 512;   // total workgroups aimed at
 static int fwd_grid_rows(long n, int nslabs, bool capped) {
-    static const int total = [] { const char *v = getenv("PDFOPS_RL_BLOCKS"); const int x = v ? atoi(v) : 0; return x > 0 ? x : 512; }();
     const int gx = fwd_row_blocks(n);
-    return capped ? std::max(1, std::min(gx, std::max(8, total / std::max(nslabs, 1)))) : gx;
+    return capped ? std::max(1, std::min(gx, std::max(8, FWD_BLOCKS / std::max(nslabs, 1)))) : gx;
 }
 
 template <int K, int NOB, int NIN, int MP>
@@ -781,7 +772,7 @@ static int launch_fwd(const FwdArgs &a, int nslabs, hipStream_t s) {   // return
     // rows (levels 4-5: 3,124 / 780 rows, up to 96 slabs for the three-output q / k / v product) one row block per 64 rows means a wave
     // loads its fragment for a single 16-row tile; fewer row blocks amortise it over several tiles.  (Not with statistics: the partial
     // rows are indexed by row block and sized by pdf_rowlin_partial_rows.)
-    // Measured (PDFOPS_RL_BLOCKS = total workgroups aimed at): 512 -> q / k / v product at 3,124 x 256: 41 -> 31 us, three-input dgrad 36 -> 30 us,
+    // Measured (FWD_BLOCKS = total workgroups aimed at): 512 -> q / k / v product at 3,124 x 256: 41 -> 31 us, three-input dgrad 36 -> 30 us,
     // 780 x 512: 54 -> 46 us, single-slab shapes unchanged; 384 and below lose on the large levels, 1024 and above change nothing.
     const int gx = fwd_grid_rows(a.N, nslabs, !stats || bst);   // (bst: the caller is told the row count)
     if constexpr (K >= 128 && NIN != 2) {
@@ -800,8 +791,8 @@ static int launch_fwd(const FwdArgs &a, int nslabs, hipStream_t s) {   // return
     return gx;
 }
 
-// rows of the statistics epilogue [row blocks][2 O] floats
 #ifdef RL2_MAIN_TU
+int stats_rows(long n) { return fwd_row_blocks(n); }
 long stats_rows_floats(long n, int o) { return (long)fwd_row_blocks(n) * 2 * o; }
 #endif
 
@@ -818,41 +809,44 @@ static int fwd_nob1(int k, int cols, bool stats, bool bst) {
     }
 }
 
-// returns 1 when a streaming kernel took the job, 0 when the shape is not covered (caller falls back to the tiled kernel)
+// THE place a forward problem is validated and its kernel arguments are made (every field of FwdArgs is set here and nowhere else);
+// false: a form or an alignment the streaming kernels do not cover.
+static bool fwd_args(const Forward &p, FwdArgs &a) {
+    const int nin = p.nin, nout = p.nout, nw = nin > 1 ? nin : nout;
+    if (nin < 1 || nout < 1 || (nin > 1 && nout > 1) || nin > 3 || nout > 3) return false;
+    if (nin == 2 && (p.scale || p.bx)) return false;   // (the two-window form: plain product only)
+    if (p.partial && !p.bx && (nin != 1 || nout != 1)) return false;
+    if (p.bx && (!p.partial || nout != 1 || p.scale || !p.bcoef || (p.ldb & 3) || !aligned16(p.bx) || !aligned16(p.bcoef))) return false;
+    if ((p.ldx & 3) || (p.ldy & 3) || (p.o & 15)) return false;
+    for (int i = 0; i < nw; ++i) if (!aligned16(p.w[i])) return false;
+    if (p.scale && (!aligned16(p.scale) || !aligned16(p.shift))) return false;
+    for (int i = 0; i < nin; ++i) if (!aligned16(p.x[i])) return false;
+    for (int i = 0; i < nout; ++i) if (!aligned16(p.y[i])) return false;
+    a = FwdArgs{};
+    a.N = p.n; a.O = p.o; a.ldx = p.ldx; a.ldy = p.ldy; a.scale = p.scale; a.shift = p.shift; a.relu = p.relu; a.accumulate = p.accumulate;
+    a.partial = p.partial; a.roww = p.roww; a.rws = p.rws;
+    a.bx = p.bx; a.ldb = p.ldb; a.bcoef = p.bcoef; a.brelu = p.brelu;
+    a.ho_gran = static_cast<unsigned long long *>(p.handoff);
+    a.ho_sync = p.handoff ? reinterpret_cast<unsigned *>(a.ho_gran + 2 * (size_t)p.o) : nullptr;
+    a.wso = p.transpose_w ? 1 : (p.ldw ? p.ldw : p.k); a.wsk = p.transpose_w ? p.o : 1;
+    for (int i = 0; i < nin; ++i) a.X[i] = p.x[i];
+    for (int i = 0; i < nw; ++i) a.W[i] = p.w[i];
+    for (int i = 0; i < nout; ++i) { a.bias[i] = p.bias[i]; a.Y[i] = p.y[i]; }
+    return true;
+}
+static bool plain1(const Forward &p) { return p.nin == 1 && p.nout == 1 && !p.scale && !p.bx && !p.roww && !p.accumulate && !p.handoff; }   // what the paired kernels take
+
 template <int MP>
-int try_forward_mp(long n, int k, int o, int nin, int nout, const float *const *x, long ldx, const float *const *w, int transpose_w,
-                   const float *const *bias, const float *scale, const float *shift, int relu, float *const *y, long ldy,
-                   int accumulate, float *partial, hipStream_t s, const float *roww, long rws, const float *bx, long ldb, const float *bcoef,
-                   int brelu, int *partial_rows, long ldw, void *handoff) {
-    if (nin < 1 || nout < 1 || (nin > 1 && nout > 1) || nin > 3 || nout > 3) return 0;
-    if (nin == 2 && (scale || bx)) return 0;   // (the two-window form: plain product only)
-    if (partial && !bx && (nin != 1 || nout != 1)) return 0;
-    if (bx && (!partial || nout != 1 || scale || !bcoef || (ldb & 3) || !aligned16(bx) || !aligned16(bcoef))) return 0;
-    if ((ldx & 3) || (ldy & 3) || (o & 15)) return 0;
-    for (int i = 0; i < (nin > 1 ? nin : nout); ++i) if (!aligned16(w[i])) return 0;
-    if (scale && (!aligned16(scale) || !aligned16(shift))) return 0;
-    for (int i = 0; i < nin; ++i) if (!aligned16(x[i])) return 0;
-    for (int i = 0; i < nout; ++i) if (!aligned16(y[i])) return 0;
+int try_forward_mp(const Forward &p, hipStream_t s, int *partial_rows) {
     FwdArgs a;
-    a.N = n; a.O = o; a.ldx = ldx; a.ldy = ldy; a.scale = scale; a.shift = shift; a.relu = relu; a.accumulate = accumulate;
-    a.partial = partial; a.roww = roww; a.rws = rws;
-    a.bx = bx; a.ldb = ldb; a.bcoef = bcoef; a.brelu = brelu;
-    a.ho_gran = static_cast<unsigned long long *>(handoff);
-    a.ho_sync = handoff ? reinterpret_cast<unsigned *>(a.ho_gran + 2 * (size_t)o) : nullptr;
-    a.wso = transpose_w ? 1 : (ldw ? ldw : k); a.wsk = transpose_w ? o : 1;   // ldw: row stride of an (o, k) window of a wider weight matrix
-    for (int i = 0; i < 3; ++i) {
-        a.X[i] = i < nin ? x[i] : nullptr;
-        a.W[i] = i < (nin > 1 ? nin : nout) ? w[i] : nullptr;
-        a.bias[i] = (bias && i < nout) ? bias[i] : nullptr;
-        a.Y[i] = i < nout ? y[i] : nullptr;
-    }
-    const int cols = o * nout;
+    if (!fwd_args(p, a)) return 0;
+    const int k = p.k, cols = p.o * p.nout;
 #define PDF_RL2(K_, NOB_, NIN_) do { if (cols % (NOB_ * 16) == 0) { \
         const int r_ = launch_fwd<K_, NOB_, NIN_, MP>(a, cols / (NOB_ * 16), s); \
         if (partial_rows) *partial_rows = r_; \
         return 1; } } while (0)
-    if (nin == 1) {
-        switch (k * 8 + fwd_nob1(k, cols, partial != nullptr, bx != nullptr)) {
+    if (p.nin == 1) {
+        switch (k * 8 + fwd_nob1(k, cols, p.partial != nullptr, p.bx != nullptr)) {
         case 32 * 8 + 6: PDF_RL2(32, 6, 1); break;
         case 32 * 8 + 2: PDF_RL2(32, 2, 1); break;
         case 32 * 8 + 1: PDF_RL2(32, 1, 1); break;
@@ -866,9 +860,9 @@ int try_forward_mp(long n, int k, int o, int nin, int nout, const float *const *
         case 512 * 8 + 1: PDF_RL2(512, 1, 1); break;
         default: break;
         }
-    } else if (nin == 2) {   // two 512-wide column windows of one 1024-wide input (ldw): ONE accumulation chain over both, bias at the end
+    } else if (p.nin == 2) {   // two 512-wide column windows of one 1024-wide input (ldw): ONE accumulation chain over both, bias at the end
         if (k == 512) PDF_RL2(512, 1, 2);
-    } else if (nin == 3) {
+    } else if (p.nin == 3) {
         switch (k) {
         case 32: PDF_RL2(32, 2, 3); break;
         case 64: PDF_RL2(64, 2, 3); break;
@@ -890,32 +884,30 @@ static bool launch_fwd_group2(const FwdArgs2 &q, unsigned total, hipStream_t s) 
     return true;
 }
 
-// Two plain products Y_i (n_i, o_i) = X_i (n_i, k) Wt_i of ONE reduction width in one launch (k_fwd2 / k_fwd_group2; transpose_w as in
-// try_forward_mp).  Paired is what a TransitionUp join reaches: both problems on the same kernel, i.e. the same slab width and the same
-// form, at the widths instantiated below.  Each problem keeps the row blocks and column slabs launch_fwd gives it; the workgroups of the
-// problem with more tiles per workgroup come first.  Returns 1 when the pair was launched; 0 when nothing was launched -- the caller
-// issues two single launches, which form the same bits.  Instantiated for fp32 operands only (rowlin2.hip: reduced-precision products
-// take the two launches).
+// Two plain products Y_i (n_i, o_i) = X_i (n_i, k) Wt_i of ONE reduction width in one launch (k_fwd2 / k_fwd_group2).  Paired is what a
+// TransitionUp join reaches: both problems on the same kernel, i.e. the same slab width and the same form, at the widths instantiated
+// below.  Each problem keeps the row blocks and column slabs launch_fwd gives it; the workgroups of the problem with more tiles per
+// workgroup come first.  Returns 1 when the pair was launched; 0 when nothing was launched -- the caller issues two single launches,
+// which form the same bits.  Instantiated for fp32 operands only (rowlin2.hip: reduced-precision products take the two launches).
 template <int MP>
-int try_forward2_mp(const long *n, int k, const int *o, const float *const *x, const float *const *w, int transpose_w, float *const *y, hipStream_t s) {
+int try_forward2_mp(const Forward (&p)[2], hipStream_t s) {
+    const int k = p[0].k;
+    if (p[1].k != k) return 0;
     FwdArgs u[2];
     int nob[2], gx[2], gy[2];
     bool group[2];
     long trips[2];
     for (int i = 0; i < 2; ++i) {
-        if (n[i] < 1 || o[i] < 16 || (o[i] & 15) || !aligned16(x[i]) || !aligned16(w[i]) || !aligned16(y[i])) return 0;
-        nob[i] = fwd_nob1(k, o[i], false, false);
+        if (!plain1(p[i]) || p[i].partial || !fwd_args(p[i], u[i])) return 0;
+        const long n = p[i].n;
+        const int o = p[i].o;
+        nob[i] = fwd_nob1(k, o, false, false);
         if (!nob[i]) return 0;
-        FwdArgs &a = u[i];
-        a.N = n[i]; a.O = o[i]; a.ldx = k; a.ldy = o[i]; a.scale = a.shift = nullptr; a.relu = 0; a.accumulate = 0; a.partial = nullptr;
-        a.roww = nullptr; a.rws = 0; a.bx = nullptr; a.ldb = 0; a.bcoef = nullptr; a.brelu = 0; a.ho_gran = nullptr; a.ho_sync = nullptr;
-        a.wso = transpose_w ? 1 : k; a.wsk = transpose_w ? o[i] : 1;
-        for (int t = 0; t < 3; ++t) { a.X[t] = t ? nullptr : x[i]; a.W[t] = t ? nullptr : w[i]; a.bias[t] = nullptr; a.Y[t] = t ? nullptr : y[i]; }
-        const int nslabs = o[i] / (nob[i] * 16);
-        gx[i] = fwd_grid_rows(n[i], nslabs, true);
-        group[i] = k >= 128 && group_form_wanted(a, k, nslabs * nob[i]);
+        const int nslabs = o / (nob[i] * 16);
+        gx[i] = fwd_grid_rows(n, nslabs, true);
+        group[i] = k >= 128 && group_form_wanted(u[i], k, nslabs * nob[i]);
         gy[i] = group[i] ? nslabs * nob[i] / GROUP_GN : nslabs;
-        trips[i] = ((n[i] + 15) / 16 + 4L * gx[i] - 1) / (4L * gx[i]);
+        trips[i] = ((n + 15) / 16 + 4L * gx[i] - 1) / (4L * gx[i]);
     }
     if (nob[0] != nob[1] || group[0] != group[1]) return 0;
     const int first = trips[1] > trips[0] ? 1 : 0;
@@ -957,24 +949,20 @@ static bool launch_fwd_stats2(const FwdArgs2 &q, unsigned total, hipStream_t s) 
 // there.  Returns 1 when the pair was launched; 0 when nothing was launched -- the caller issues two single launches, which form the
 // same bits.  Instantiated for fp32 operands only (rowlin2.hip).
 template <int MP>
-int try_forward_stats2_mp(const long *n, const int *k, int o, const float *const *x, const float *const *w, const float *const *bias, float *const *y,
-                          float *const *partial, hipStream_t s) {
-    if (o < 16 || (o & 15)) return 0;
+int try_forward_stats2_mp(const Forward (&p)[2], hipStream_t s) {
+    const int o = p[0].o;
+    if (p[1].o != o) return 0;
     FwdArgs2 q;
-    int nb[2], gy[2];
+    int k[2], nb[2], gy[2];
     bool group[2];
     for (int i = 0; i < 2; ++i) {
-        if (n[i] < 1 || !aligned16(x[i]) || !aligned16(w[i]) || !aligned16(y[i]) || !partial[i]) return 0;
+        if (!plain1(p[i]) || !p[i].partial || p[i].transpose_w || !fwd_args(p[i], q.a[i])) return 0;
+        k[i] = p[i].k;
         const int nob = fwd_nob1(k[i], o, true, false);
         if (!nob) return 0;
-        FwdArgs &a = q.a[i];
-        a.N = n[i]; a.O = o; a.ldx = k[i]; a.ldy = o; a.scale = a.shift = nullptr; a.relu = 0; a.accumulate = 0; a.partial = partial[i];
-        a.roww = nullptr; a.rws = 0; a.bx = nullptr; a.ldb = 0; a.bcoef = nullptr; a.brelu = 0; a.ho_gran = nullptr; a.ho_sync = nullptr;
-        a.wso = k[i]; a.wsk = 1;
-        for (int t = 0; t < 3; ++t) { a.X[t] = t ? nullptr : x[i]; a.W[t] = t ? nullptr : w[i]; a.bias[t] = t ? nullptr : bias[i]; a.Y[t] = t ? nullptr : y[i]; }
         const int blocks = o / 16;
-        q.gx[i] = (unsigned)fwd_grid_rows(n[i], blocks / nob, false);
-        group[i] = k[i] >= 128 && group_form_wanted(a, k[i], blocks);
+        q.gx[i] = (unsigned)fwd_grid_rows(p[i].n, blocks / nob, false);
+        group[i] = k[i] >= 128 && group_form_wanted(q.a[i], k[i], blocks);
         nb[i] = group[i] ? GROUP_GN : nob;
         gy[i] = blocks / nb[i];
     }
@@ -992,53 +980,65 @@ int try_forward_stats2_mp(const long *n, const int *k, int o, const float *const
     return 0;
 }
 
-// Arguments, grid and reduction of one k_wg launch over gradients that share the layer input; false: the shape or an alignment is not covered.
+// THE place the arguments, grid and reduction of a k_wg launch are made, from the plan that sized the workspace (every field of WArgs
+// and RArgs is set here and nowhere else); false: the shape or an alignment is not covered.
 struct WgSetup { WArgs a; RArgs r; dim3 grid; int vw; bool any_bias; };
-static bool wgrad_setup(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale, const float *shift,
-                        int relu, float *const *dw, float *const *db, float *ws, const float *roww, long rws, WgSetup &u) {
-    if (ng < 1 || ng > 3 || !ws) return false;
-    const WgPlan p = wg_plan(n, k, o, ng);
-    const int vw = p.vw;
+static bool wg_setup(const Wgrad &p, WgSetup &u) {
+    const bool pz = p.per_gradient;
+    if (p.ng < 1 || p.ng > (pz ? WG_MAXG : 3) || !p.ws) return false;
+    const WgPlan pl = wg_plan(p.n, p.k, p.o, p.ng);
+    const int vw = pl.vw, b = pl.b;
     if (!vw) return false;
-    if ((ldg % vw) || (ldx % vw) || !aligned16(x)) return false;
-    if (scale && (!aligned16(scale) || !aligned16(shift))) return false;
-    for (int i = 0; i < ng; ++i) if (!aligned16(g[i])) return false;
+    if ((p.ldg % vw) || (p.ldx % vw)) return false;
+    if (pz) {
+        if (p.roww) return false;   // (no kernel is instantiated for per-gradient inputs with a row weight)
+    } else {
+        if (!aligned16(p.x)) return false;
+        if (p.scale && (!aligned16(p.scale) || !aligned16(p.shift))) return false;
+    }
+    for (int i = 0; i < p.ng; ++i) {
+        if (!aligned16(p.g[i])) return false;
+        if (pz && (!aligned16(p.xz[i]) || (p.scalez[i] && (!aligned16(p.scalez[i]) || !aligned16(p.shiftz[i]))))) return false;
+    }
+    u = WgSetup{};
     WArgs &a = u.a;
-    a.N = n; a.K = k; a.O = o; a.ldg = ldg; a.X = x; a.ldx = ldx; a.scale = scale; a.shift = shift; a.relu = relu; a.roww = roww; a.rws = rws;
-    a.per_z = 0;
-    u.any_bias = false;
-    for (int i = 0; i < WG_MAXG; ++i) {
-        a.G[i] = i < ng ? g[i] : nullptr; a.dW[i] = i < ng ? dw[i] : nullptr; a.db[i] = (db && i < ng) ? db[i] : nullptr;
-        a.Xz[i] = nullptr; a.scalez[i] = a.shiftz[i] = nullptr; a.reluz[i] = 0;
+    a.N = p.n; a.K = p.k; a.O = p.o; a.ldg = p.ldg; a.ldx = p.ldx; a.roww = p.roww; a.rws = p.rws;
+    a.per_z = pz ? 1 : 0;
+    if (!pz) { a.X = p.x; a.scale = p.scale; a.shift = p.shift; a.relu = p.relu; }
+    for (int i = 0; i < p.ng; ++i) {
+        a.G[i] = p.g[i]; a.dW[i] = p.dw[i]; a.db[i] = p.db[i];
+        if (pz) { a.Xz[i] = p.xz[i]; a.scalez[i] = p.scalez[i]; a.shiftz[i] = p.shiftz[i]; a.reluz[i] = p.reluz[i]; }
         u.any_bias = u.any_bias || a.db[i] != nullptr;
     }
-    const int b = p.b;
-    a.rows_per_block = p.rows_per_block;
-    a.slab = ws;
-    a.bslab = ws + (size_t)p.nblk * p.split * b * b;
+    a.rows_per_block = pl.rows_per_block;
+    a.slab = p.ws + pl.slab;
+    a.bslab = p.ws + pl.bslab;
     u.vw = vw;
-    u.grid = dim3((unsigned)p.split, (unsigned)((o / b) * (k / b)), (unsigned)ng);
+    u.grid = dim3((unsigned)pl.split, (unsigned)((p.o / b) * (p.k / b)), (unsigned)p.ng);
     RArgs &r = u.r;
-    r.slab = a.slab; r.bslab = a.bslab; r.B = b; r.tiles_k = k / b; r.tiles = (o / b) * (k / b); r.otiles = o / b; r.split = (int)p.split; r.K = k; r.O = o;
+    r.slab = a.slab; r.bslab = a.bslab; r.B = b; r.tiles_k = p.k / b; r.tiles = (p.o / b) * (p.k / b); r.otiles = p.o / b; r.split = (int)pl.split;
+    r.K = p.k; r.O = p.o;
     for (int i = 0; i < WG_MAXG; ++i) { r.dW[i] = a.dW[i]; r.db[i] = a.db[i]; }
     return true;
 }
 
+// One k_wg launch + one slab reduction, for gradients that share the layer input and for up to WG_MAXG gradients of ONE shape with their
+// OWN inputs (Wgrad::per_gradient; kernels with the prologue, which a null scalez[i] runs as the identity).  A Bottleneck's backward has
+// five such products (linear3, q / k / v, linear1: all c x c over the block's n rows); issued one by one at levels 3-5 each of them is a
+// launch that fills a fraction of the chip followed by its own reduction launch.
 template <int MP>
-int try_wgrad_mp(long n, int k, int o, int ng, const float *const *g, long ldg, const float *x, long ldx, const float *scale,
-                 const float *shift, int relu, float *const *dw, float *const *db, float *ws, hipStream_t s, const float *roww, long rws,
-                 RArgs *defer) {   // defer: the slab reduction is not launched, its arguments are handed back (launch_slab_reduce2)
+int try_wgrad_mp(const Wgrad &p, hipStream_t s) {
     WgSetup u;
-    if (!wgrad_setup(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, roww, rws, u)) return 0;
+    if (!wg_setup(p, u)) return 0;
     const WArgs &a = u.a;
     const dim3 grid = u.grid;
+    const bool pre = p.per_gradient || p.scale != nullptr;
 #define PDF_WG(VW_) do { \
-        if (roww) { if (scale) k_wg<VW_, true, true, MP><<<grid, 256, 0, s>>>(a); else k_wg<VW_, false, true, MP><<<grid, 256, 0, s>>>(a); } \
-        else      { if (scale) k_wg<VW_, true, false, MP><<<grid, 256, 0, s>>>(a); else k_wg<VW_, false, false, MP><<<grid, 256, 0, s>>>(a); } } while (0)
+        if (p.roww) { if (pre) k_wg<VW_, true, true, MP><<<grid, 256, 0, s>>>(a); else k_wg<VW_, false, true, MP><<<grid, 256, 0, s>>>(a); } \
+        else        { if (pre) k_wg<VW_, true, false, MP><<<grid, 256, 0, s>>>(a); else k_wg<VW_, false, false, MP><<<grid, 256, 0, s>>>(a); } } while (0)
     if (u.vw == 4) PDF_WG(4); else PDF_WG(2);
 #undef PDF_WG
-    if (defer) *defer = u.r;
-    else launch_slab_reduce(u.r, ng, u.any_bias, s);
+    launch_slab_reduce(u.r, p.ng, u.any_bias, s);
     return 1;
 }
 
@@ -1048,11 +1048,10 @@ int try_wgrad_mp(long n, int k, int o, int ng, const float *const *g, long ldg, 
 // wg_block over the grid of its own problem: the same slabs.  Returns 2 for one launch, 1 for two; 0: a shape or an alignment is not covered,
 // nothing was launched.
 template <int MP>
-int try_wgrad_pair_mp(const long *n, const int *k, const int *o, const float *const *g, const float *const *x, float *const *dw, float *const *db,
-                      float *const *ws, bool pair, hipStream_t s, RArgs *r) {
+int try_wgrad_pair_mp(const Wgrad (&p)[2], bool pair, hipStream_t s, RArgs *r) {
     WgSetup u[2];
     for (int i = 0; i < 2; ++i)
-        if (!wgrad_setup(n[i], k[i], o[i], 1, &g[i], o[i], x[i], k[i], nullptr, nullptr, 0, &dw[i], &db[i], ws[i], nullptr, 0, u[i])) return 0;
+        if (p[i].ng != 1 || p[i].per_gradient || p[i].scale || p[i].roww || !wg_setup(p[i], u[i])) return 0;
     r[0] = u[0].r; r[1] = u[1].r;
     if constexpr (MP == 0) {   // (the paired kernel is built for fp32 operands only: reduced-precision products take one launch each)
         if (pair && u[0].vw == u[1].vw) {
@@ -1070,50 +1069,5 @@ int try_wgrad_pair_mp(const long *n, const int *k, const int *o, const float *co
     }
     return 1;
 }
-
-// Up to WG_MAXG weight gradients of ONE shape (n, k, o) with their OWN inputs in one launch + one slab reduction: dW_i = G_i^T f_i(X_i),
-// f_i = relu?(x * scale_i + shift_i) where scale_i is non-null, the identity otherwise.  A Bottleneck's backward has five such products
-// (linear3, q / k / v, linear1: all c x c over the block's n rows); issued one by one at levels 3-5 each of them is a launch that fills a
-// fraction of the chip followed by its own reduction launch.  ws: wgrad_ws_floats(n, k, o, ng) floats.
-template <int MP>
-int try_wgrad_group_mp(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx,
-                       const float *const *scale, const float *const *shift, const int *relu, float *const *dw, float *const *db,
-                       float *ws, hipStream_t s) {
-    if (ng < 1 || ng > WG_MAXG || !ws) return 0;
-    const WgPlan p = wg_plan(n, k, o, ng);
-    const int vw = p.vw;
-    if (!vw) return 0;
-    if ((ldg % vw) || (ldx % vw)) return 0;
-    for (int i = 0; i < ng; ++i) {
-        if (!aligned16(g[i]) || !aligned16(x[i])) return 0;
-        if (scale[i] && (!aligned16(scale[i]) || !aligned16(shift[i]))) return 0;
-    }
-    WArgs a;
-    a.N = n; a.K = k; a.O = o; a.ldg = ldg; a.X = nullptr; a.ldx = ldx; a.scale = a.shift = nullptr; a.relu = 0; a.roww = nullptr; a.rws = 0;
-    a.per_z = 1;
-    bool any_bias = false;
-    for (int i = 0; i < WG_MAXG; ++i) {
-        const bool on = i < ng;
-        a.G[i] = on ? g[i] : nullptr; a.Xz[i] = on ? x[i] : nullptr;
-        a.scalez[i] = on ? scale[i] : nullptr; a.shiftz[i] = on ? shift[i] : nullptr; a.reluz[i] = on ? relu[i] : 0;
-        a.dW[i] = on ? dw[i] : nullptr; a.db[i] = (on && db) ? db[i] : nullptr;
-        any_bias = any_bias || a.db[i] != nullptr;
-    }
-    const int b = p.b;
-    a.rows_per_block = p.rows_per_block;
-    a.slab = ws;
-    a.bslab = ws + (size_t)p.nblk * p.split * b * b;
-    const dim3 grid((unsigned)p.split, (unsigned)((o / b) * (k / b)), (unsigned)ng);
-    if (vw == 4) k_wg<4, true, false, MP><<<grid, 256, 0, s>>>(a); else k_wg<2, true, false, MP><<<grid, 256, 0, s>>>(a);
-    RArgs r;
-    r.slab = a.slab; r.bslab = a.bslab; r.B = b; r.tiles_k = k / b; r.tiles = (o / b) * (k / b); r.otiles = o / b; r.split = (int)p.split; r.K = k; r.O = o;
-    for (int i = 0; i < WG_MAXG; ++i) { r.dW[i] = a.dW[i]; r.db[i] = a.db[i]; }
-    launch_slab_reduce(r, ng, any_bias, s);
-    return 1;
-}
-
-#ifdef RL2_MAIN_TU
-int stats_rows(long n) { return fwd_row_blocks(n); }
-#endif
 
 }  // namespace rl2
