@@ -57,8 +57,9 @@ extern "C" {
  * 18 = pdf_pg_* and PDF_ERR_NOT_CONVERGED added (no existing parameter list changed);
  * 19 = pdf_transition_up_* and the two-problem entries pdf_bn_coef_from_partial2 / pdf_bn_act_backward2 / pdf_rowlin_wgrad2 added (no
  *      existing parameter list changed);
- * 20 = pdf_rowlin_forward_stats2 / pdf_rowlin_dgrad2 / pdf_rowlin_wgrad2_paired added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 20
+ * 20 = pdf_rowlin_forward_stats2 / pdf_rowlin_dgrad2 / pdf_rowlin_wgrad2_paired added (no existing parameter list changed);
+ * 21 = pdf_msc_* added (no existing parameter list changed). */
+#define PDF_ABI_VERSION 21
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -1050,6 +1051,37 @@ long pdf_pg_bias_loss_workspace_doubles(void);
 int pdf_pg_bias_loss_forward(long n, const float *pred, const float *coord, const void *centroid, int centroid_f64, const long long *instance,
                              long long ignore, float *d1, float *d2, double *acc, void *loss, void *stream);
 int pdf_pg_bias_loss_backward(long n, const float *d1, const float *d2, const double *acc, const void *gy, int f64, float *grad, void *stream);
+
+/* ---- csrc/scene_contrast.hip: MSC-v1m1 (pointcept/models/masked_scene_contrast/masked_scene_contrast_v1m1_base.py) -------------------------
+ * Matched-pair InfoNCE (:174-203) without a (p, p) array.  feat1 (n1, c), feat2 (n2, c) fp32, match (p, 2) int64 = rows of the two views
+ * (an index outside its view acts as a zero row and receives no gradient), c a multiple of 32 up to 256 (pdf_msc_nce_supported), p >= 1.
+ * Forward: out (3) = {loss = mean_i(lse_i - s_ii / t), pos_sim = mean_i s_ii, neg_sim = mean_i mean_j s_ij - pos_sim / p} with
+ *   S = A^ B^T, A^ = a / (|a| + 1e-7) over the gathered rows; saved = pdf_msc_nce_saved_floats(p, c) floats (A^, B^, norms, lse: what the
+ *   backward reads), workspace = pdf_msc_nce_workspace_bytes(p, c, 0) bytes, 256-byte aligned, nothing to zero.
+ * Backward: g1 (n1, c), g2 (n2, c) = gy[0] * d loss / d feat, every row written (zeros where no pair points); a row matched by several
+ *   pairs adds them in ascending pair order; workspace = pdf_msc_nce_workspace_bytes(p, c, 1) bytes.  No atomics, no memset, no host read:
+ *   the order of every sum is a function of p and c. */
+int pdf_msc_nce_supported(int c);
+long pdf_msc_nce_saved_floats(long p, int c);
+long pdf_msc_nce_workspace_bytes(long p, int c, int backward);
+int pdf_msc_nce_forward(long p, int c, long n1, long n2, const float *feat1, const float *feat2, const long long *match, float temperature,
+                        float *saved, float *out, void *workspace, long workspace_bytes, void *stream);
+int pdf_msc_nce_backward(long p, int c, long n1, long n2, const float *feat1, const float *feat2, const long long *match, float temperature,
+                         const float *saved, const float *gy, float *g1, float *g2, void *workspace, long workspace_bytes, void *stream);
+/* Masked reconstruction head (:274-307) over both views: pred = feat weight^T + bias (weight (3, c), c as above) on the rows whose mask
+ * byte is set; kind 0 (color): term = sum (pred - target)^2, kind 1 (normal): term = sum pred / (|pred| + 1e-10) * target;
+ * loss (1) = sum of the terms / masked rows (NaN without one).  dpred (n1 + n2, 3) = d term / d pred of the masked rows, acc =
+ * pdf_msc_recon_acc_doubles() doubles (acc[0] = 1 / masked rows), both read by the backward: g1, g2 = d feat (zero rows where unmasked),
+ * gw (3, c), gb (3) from per-workgroup slabs (slab: pdf_msc_recon_slab_floats(n1 + n2, c) floats) added in slab order.  gy (1) on the device. */
+int pdf_msc_recon_supported(int c);
+long pdf_msc_recon_acc_doubles(void);
+long pdf_msc_recon_slab_floats(long n, int c);
+int pdf_msc_recon_forward(long n1, long n2, int c, int kind, const float *feat1, const float *feat2, const unsigned char *mask1,
+                          const unsigned char *mask2, const float *weight, const float *bias, const float *target1, const float *target2,
+                          float *dpred, double *acc, float *loss, void *stream);
+int pdf_msc_recon_backward(long n1, long n2, int c, const float *feat1, const float *feat2, const unsigned char *mask1, const unsigned char *mask2,
+                           const float *weight, const float *dpred, const double *acc, const float *gy, float *g1, float *g2, float *gw, float *gb,
+                           float *slab, void *stream);
 
 #ifdef __cplusplus
 }

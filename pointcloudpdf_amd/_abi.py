@@ -298,6 +298,17 @@ ENTRIES = {
     "pdf_pg_bias_loss_workspace_doubles": ("l", ""),
     "pdf_pg_bias_loss_forward": ("s", "lpppiplppppp"),
     "pdf_pg_bias_loss_backward": ("s", "lppppipp"),
+    # csrc/scene_contrast.hip
+    "pdf_msc_nce_supported": ("i", "i"),
+    "pdf_msc_nce_saved_floats": ("l", "li"),
+    "pdf_msc_nce_workspace_bytes": ("l", "lii"),
+    "pdf_msc_nce_forward": ("s", "lillpppfppplp"),
+    "pdf_msc_nce_backward": ("s", "lillpppfppppplp"),
+    "pdf_msc_recon_supported": ("i", "i"),
+    "pdf_msc_recon_acc_doubles": ("l", ""),
+    "pdf_msc_recon_slab_floats": ("l", "li"),
+    "pdf_msc_recon_forward": ("s", "llii" + "p" * 12),
+    "pdf_msc_recon_backward": ("s", "lli" + "p" * 14),
 }
 
 

@@ -28,7 +28,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 20   # include/pdfops.h: PDF_ABI_VERSION (the rows of _abi.ENTRIES are THIS version's parameter lists)
+ABI_VERSION = 21  # include/pdfops.h: PDF_ABI_VERSION (the rows of _abi.ENTRIES are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_void_p = ctypes.c_void_p
@@ -2206,6 +2206,80 @@ class HipBackend(CBackend):
         if n:
             self._call("pg_bias_loss_backward", n, d[0], d[1], acc, gy.contiguous(), int(gy.dtype == torch.float64), grad)
         return grad
+
+    # -- csrc/scene_contrast.hip (MSC-v1m1) ---------------------------------------------------------------------------------------------
+    def msc_nce_supported(self, c):
+        return bool(self.lib.pdf_msc_nce_supported(int(c)))
+
+    @staticmethod
+    def _msc_nce_check(feat1, feat2, match):
+        _check(feat1, torch.float32, "feat1"); _check(feat2, torch.float32, "feat2"); _check(match, torch.int64, "match_index")
+        p, c = int(match.shape[0]), int(feat1.shape[1])
+        if feat1.dim() != 2 or tuple(feat2.shape[1:]) != (c,) or tuple(match.shape) != (p, 2) or p < 1:
+            raise ValueError("msc_nce: feat1 (n1, c), feat2 (n2, c) and match_index (p >= 1, 2)")
+        return p, c
+
+    def msc_nce_forward(self, feat1, feat2, match, temperature):
+        """-> out (3) = {loss, pos_sim, neg_sim}, saved (what the backward reads: normalised rows, norms, lse)."""
+        p, c = self._msc_nce_check(feat1, feat2, match)
+        dev = feat1.device
+        saved = torch.empty(int(self.lib.pdf_msc_nce_saved_floats(p, c)), dtype=torch.float32, device=dev)
+        nbytes = int(self.lib.pdf_msc_nce_workspace_bytes(p, c, 0))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        self._call("msc_nce_forward", p, c, int(feat1.shape[0]), int(feat2.shape[0]), feat1, feat2, match, float(temperature), saved, out, ws, nbytes)
+        return out, saved
+
+    def msc_nce_backward(self, feat1, feat2, match, temperature, saved, gy):
+        """-> d feat1, d feat2: every row written by the pass (no memset in front)."""
+        p, c = self._msc_nce_check(feat1, feat2, match)
+        _check(gy, torch.float32, "grad of the loss")
+        dev = feat1.device
+        g1, g2 = torch.empty_like(feat1), torch.empty_like(feat2)
+        nbytes = int(self.lib.pdf_msc_nce_workspace_bytes(p, c, 1))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._call("msc_nce_backward", p, c, int(feat1.shape[0]), int(feat2.shape[0]), feat1, feat2, match, float(temperature), saved, gy,
+                   g1 if g1.numel() else None, g2 if g2.numel() else None, ws, nbytes)
+        return g1, g2
+
+    def msc_recon_supported(self, c):
+        return bool(self.lib.pdf_msc_recon_supported(int(c)))
+
+    @staticmethod
+    def _msc_recon_check(feat1, feat2, mask1, mask2, weight):
+        _check(feat1, torch.float32, "view1 feat"); _check(feat2, torch.float32, "view2 feat"); _check(weight, torch.float32, "weight")
+        _check(mask1, torch.bool, "view1 mask"); _check(mask2, torch.bool, "view2 mask")
+        n1, n2, c = int(feat1.shape[0]), int(feat2.shape[0]), int(weight.shape[1])
+        if (tuple(feat1.shape) != (n1, c) or tuple(feat2.shape) != (n2, c) or tuple(weight.shape) != (3, c) or tuple(mask1.shape) != (n1,)
+                or tuple(mask2.shape) != (n2,)):
+            raise ValueError("msc_recon: feat (n, c), masks (n), weight (3, c)")
+        return n1, n2, c
+
+    def msc_recon_forward(self, kind, feat1, feat2, mask1, mask2, weight, bias, target1, target2):
+        """kind 0 color / 1 normal -> loss (1), dpred (n1 + n2, 3), acc (the backward's state)."""
+        n1, n2, c = self._msc_recon_check(feat1, feat2, mask1, mask2, weight)
+        _check(bias, torch.float32, "bias"); _check(target1, torch.float32, "view1 target"); _check(target2, torch.float32, "view2 target")
+        if tuple(bias.shape) != (3,) or tuple(target1.shape) != (n1, 3) or tuple(target2.shape) != (n2, 3):
+            raise ValueError("msc_recon: bias (3), targets (n, 3)")
+        dev = weight.device
+        dpred = torch.empty((n1 + n2, 3), dtype=torch.float32, device=dev)
+        acc = torch.empty(int(self.lib.pdf_msc_recon_acc_doubles()), dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        self._call("msc_recon_forward", n1, n2, c, int(kind), feat1 if n1 else None, feat2 if n2 else None, mask1 if n1 else None,
+                   mask2 if n2 else None, weight, bias, target1 if n1 else None, target2 if n2 else None, dpred if n1 + n2 else None, acc, loss)
+        return loss, dpred, acc
+
+    def msc_recon_backward(self, feat1, feat2, mask1, mask2, weight, dpred, acc, gy):
+        """-> d feat1, d feat2 (zero rows where unmasked), d weight (3, c), d bias (3)."""
+        n1, n2, c = self._msc_recon_check(feat1, feat2, mask1, mask2, weight)
+        _check(gy, torch.float32, "grad of the loss")
+        dev = weight.device
+        g1, g2 = torch.empty_like(feat1), torch.empty_like(feat2)
+        gw, gb = torch.empty_like(weight), torch.empty(3, dtype=torch.float32, device=dev)
+        slab = torch.empty(int(self.lib.pdf_msc_recon_slab_floats(n1 + n2, c)), dtype=torch.float32, device=dev)
+        self._call("msc_recon_backward", n1, n2, c, feat1 if n1 else None, feat2 if n2 else None, mask1 if n1 else None, mask2 if n2 else None,
+                   weight, dpred if n1 + n2 else None, acc, gy, g1 if n1 else None, g2 if n2 else None, gw, gb, slab)
+        return g1, g2, gw, gb
 
 
 _lock = threading.Lock()

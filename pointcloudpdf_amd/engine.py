@@ -175,8 +175,8 @@ class SegStep(nn.Module):
 
 
 def build_seg_step(cfg):
-    """``SegStep`` of a reference config that has only a ``model`` section (configs/*/semseg-*.py, insseg-pointgroup-*.py; dict or attribute access)."""
-    from . import cac, point_group, point_transformer_v2, point_transformer_v3, sparse_unet, stratified  # noqa: F401  (register CAC-v1m1, PG-v1m1, PT-v2m2, PT-v3m1, SpUNet-v1m1, ST-v1m1)
+    """``SegStep`` of a reference config that has only a ``model`` section (configs/*/semseg-*.py, insseg-pointgroup-*.py, pretrain-msc-v1m1-*.py; dict or attribute access)."""
+    from . import cac, masked_scene_contrast, point_group, point_transformer_v2, point_transformer_v3, sparse_unet, stratified  # noqa: F401  (register CAC-v1m1, MSC-v1m1, PG-v1m1, PT-v2m2, PT-v3m1, SpUNet-v1m1, ST-v1m1)
 
     model_cfg = _cfg_get(cfg, "model")
     if model_cfg is None:

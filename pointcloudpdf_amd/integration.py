@@ -19,11 +19,11 @@ def install_pointops():
 def register_into_pointcept(force=True):
     """Register our classes under the reference's names in a live pointcept install's registries."""
     from pointcept.models.builder import MODELS as PC_MODELS  # noqa: import error = pointcept not importable
-    from . import cac, point_group, point_transformer, point_transformer_v2, point_transformer_v3, recognizer, segmentor, model_hook, sparse_unet, stratified  # noqa: F401  (fills the registries)
+    from . import cac, masked_scene_contrast, point_group, point_transformer, point_transformer_v2, point_transformer_v3, recognizer, segmentor, model_hook, sparse_unet, stratified  # noqa: F401  (fills the registries)
     from .registry import MODELS, RECOGNIZER, MODELHOOKS
 
     for name in ["PointTransformer-Seg26", "PointTransformer-Seg38", "PointTransformer-Seg50",
-                 "PointTransformer-Recognizer", "ST-v1m1", "ST-v1m1-Recognizer", "PT-v2m2", "DefaultSegmentor", "CAC-v1m1", "SpUNet-v1m1", "PT-v3m1", "DefaultSegmentorV2", "PG-v1m1"]:
+                 "PointTransformer-Recognizer", "ST-v1m1", "ST-v1m1-Recognizer", "PT-v2m2", "DefaultSegmentor", "CAC-v1m1", "SpUNet-v1m1", "PT-v3m1", "DefaultSegmentorV2", "PG-v1m1", "MSC-v1m1"]:
         PC_MODELS.register_module(name=name, force=force, module=MODELS.get(name))
     try:
         from pointcept.recognizers.builder import RECOGNIZER as PC_REC

@@ -427,3 +427,62 @@ class DiceLoss(nn.Module):
         else:
             loss = dice_loss_reference(pred, target.long(), self.smooth, self.exponent, self.ignore_index)
         return self.loss_weight * loss
+
+
+# ---- matched-pair InfoNCE (MSC-v1m1) -------------------------------------------------------------------------------------------------
+def matched_info_nce_reference(feat1, feat2, match_index, temperature):
+    """The reference's ``compute_contrastive_loss`` (masked_scene_contrast_v1m1_base.py:179-193) as it is written: gather, normalise,
+    the (P, P) similarity matrix, cross-entropy against the diagonal -> (loss, pos_sim, neg_sim)."""
+    a = feat1[match_index[:, 0]]
+    b = feat2[match_index[:, 1]]
+    a = a / (torch.norm(a, p=2, dim=1, keepdim=True) + 1e-7)
+    b = b / (torch.norm(b, p=2, dim=1, keepdim=True) + 1e-7)
+    sim = torch.mm(a, b.transpose(1, 0))
+    with torch.no_grad():
+        pos_sim = torch.diagonal(sim).mean()
+        neg_sim = sim.mean(dim=-1).mean() - pos_sim / match_index.shape[0]
+    labels = torch.arange(sim.shape[0], device=a.device).long()
+    loss = F.cross_entropy(torch.div(sim, temperature), labels, reduction="mean")
+    return loss, pos_sim, neg_sim
+
+
+class _FusedInfoNCE(torch.autograd.Function):
+    """csrc/scene_contrast.hip: the similarity tiles are formed on the matrix cores and folded into running row statistics; the backward
+    recomputes them.  No (P, P) array in either direction, no atomics: two evaluations are bit-identical."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, feat1, feat2, match_index, temperature):
+        from . import _native
+
+        feat1, feat2, match_index = feat1.contiguous(), feat2.contiguous(), match_index.contiguous()
+        out, saved = _native.hip_backend().msc_nce_forward(feat1, feat2, match_index, temperature)
+        ctx.save_for_backward(feat1, feat2, match_index, saved)
+        ctx.temperature = float(temperature)
+        loss, pos_sim, neg_sim = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(pos_sim, neg_sim)
+        return loss, pos_sim, neg_sim
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy, _gpos, _gneg):
+        from . import _native
+
+        feat1, feat2, match_index, saved = ctx.saved_tensors
+        g1, g2 = _native.hip_backend().msc_nce_backward(feat1, feat2, match_index, ctx.temperature, saved, gy.contiguous().float().reshape(1))
+        return g1, g2, None, None
+
+
+def matched_info_nce(feat1, feat2, match_index, temperature):
+    """InfoNCE over the matched rows of two views -> (loss, pos_sim, neg_sim), 0-dim; ``pos_sim`` / ``neg_sim`` carry no gradient.
+    fp32 device tensors with C a multiple of 32 up to 256 and at least one pair run as one node of the HIP library; anything else takes
+    ``matched_info_nce_reference``."""
+    from . import _native
+
+    fused = (feat1.is_cuda and feat1.dtype == torch.float32 and feat2.dtype == torch.float32 and feat1.dim() == 2 and feat2.dim() == 2
+             and feat1.shape[1] == feat2.shape[1] and match_index.dtype == torch.int64 and match_index.shape[0] >= 1
+             and _native.hip_backend().msc_nce_supported(feat1.shape[1]))
+    if not fused:
+        return matched_info_nce_reference(feat1, feat2, match_index, temperature)
+    _native.require_current_device(feat1, feat2, match_index)
+    return _FusedInfoNCE.apply(feat1, feat2, match_index, float(temperature))
