@@ -49,12 +49,6 @@ inline int cac_chunks(long n, int scenes) {
     return (int)(g < 1 ? 1 : g > MAX_CHUNKS ? MAX_CHUNKS : g);
 }
 
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // rows [r0, r1) of chunk ch of scene s (offset == nullptr: one scene of n rows); step = the pass's row step
 __device__ __forceinline__ void chunk_rows(long n, const int *__restrict__ offset, int s, int ch, int nch, int step, long &r0, long &r1) {
     long a = 0, b = n;
@@ -80,7 +74,7 @@ __device__ __forceinline__ void soft_weights(const float *__restrict__ x, bool l
     }
     float m = -__builtin_huge_valf();
     for (int k = lane; k < K; k += 64) m = fmaxf(m, x[k]);
-    m = wave_max_f32(m);
+    m = pdf_wave_max_f32(m);
     float s = 0.f;
     for (int k = lane; k < K; k += 64) s += expf(x[k] - m);
     s = pdf_wave_sum_f32(s);
@@ -398,7 +392,7 @@ __global__ __launch_bounds__(LB) void k_distill_row(long n, int K, const float *
         const long hot = valid ? t : 0;   // (the reference scatters ignored rows into class 0; their entropy weight is 0)
         float mx = -__builtin_huge_valf(), my = -__builtin_huge_valf();
         for (int k = lane; k < K; k += 64) { mx = fmaxf(mx, x[k]); my = fmaxf(my, y[k]); }
-        mx = wave_max_f32(mx); my = wave_max_f32(my);
+        mx = pdf_wave_max_f32(mx); my = pdf_wave_max_f32(my);
         float sx = 0.f, sy = 0.f;
         for (int k = lane; k < K; k += 64) { sx += expf(x[k] - mx); sy += expf(y[k] - my); }
         sx = pdf_wave_sum_f32(sx); sy = pdf_wave_sum_f32(sy);

@@ -1,17 +1,16 @@
 // The remaining criteria of pointcept/models/losses/misc.py as capturable passes: the full nn.CrossEntropyLoss (class weights, label
 // smoothing, mean / sum / none, any class count), FocalLoss (:97-172), DiceLoss (:176-223) and BinaryFocalLoss (:60-93).  The plain
-// cross-entropy of csrc/loss.hip is untouched.  Rules shared with loss.hip / lovasz.hip: fp32 logits, int64 labels, wave64; no float
-// atomics -- every workgroup leaves its partial sums in its own slot and ONE workgroup adds the slots in a fixed order (in double), so
-// every pass is bit-reproducible; nothing needs zeroing; nothing is read back to the host (the reference selects rows with a boolean
-// mask and branches on len(target) == 0).  Every forward leaves its UNSCALED gradient (dice: the softmax) in a buffer that the backward
-// only reads, so retain_graph / a second backward see the same values.
+// cross-entropy of csrc/loss.hip is untouched.  Rules shared with loss.hip / lovasz.hip: fp32 logits, int64 labels, wave64; the slot
+// sums of slot_sum.h in double (by waves into the workgroup's slot, one workgroup totals the slots); nothing needs zeroing; nothing is
+// read back to the host (the reference selects rows with a boolean mask and branches on len(target) == 0).  Every forward leaves its
+// UNSCALED gradient (dice: the softmax) in a buffer that the backward only reads, so retain_graph / a second backward see the same values.
 //
 //   acc = [sum, normaliser, scale, -] | per-workgroup [sum | normaliser] pairs of doubles            (CE, focal, binary focal)
 //   acc = [loss, -, -, -] | coefficients (2, c): d loss / d p = ca[j] y + cb[j] p^(exponent - 1) | partial slabs (blocks, 3, c)   (dice)
 //
 // Row passes (CE, dice): c <= 64 one lane per row (as k_ce_fwd), above that one wave per row with strided columns and wave reductions.
 // Bound: HBM for every kernel here (CE 8NC bytes forward, focal 8NC, dice 12NC).
-#include "pdfops_common.h"
+#include "slot_sum.h"
 
 namespace {
 
@@ -21,48 +20,21 @@ constexpr int MAX_BLOCKS = 1024;    // row / element passes: at most this many w
 constexpr int DICE_BLOCKS = 512;    // dice column sums: at most this many row chunks, one (3, c) slab of floats each
 enum { FIN_SUM = 0, FIN_MEAN = 1, FIN_MEAN_OR_ZERO = 2 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __device__ __forceinline__ double *pair_slots(float *acc) { return reinterpret_cast<double *>(acc + HEAD); }
 
-// the workgroup's [a | b] into its own slot (every thread of the block calls it)
+// the workgroup's [a | b] by waves into its own slot (every thread of the block calls it)
 __device__ __forceinline__ void block_pair_store(double a, double b, float *acc) {
-    __shared__ double red[2][LB / 64];
-    a = wave_sum_f64(a);
-    b = wave_sum_f64(b);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = 0.0; b = 0.0;
-        for (int w = 0; w < LB / 64; ++w) { a += red[0][w]; b += red[1][w]; }
-        double *part = pair_slots(acc);
-        part[2 * blockIdx.x] = a;
-        part[2 * blockIdx.x + 1] = b;
-    }
+    double v[2] = {a, b};
+    block_sum_by_waves<LB>(v, pair_slots(acc) + 2 * blockIdx.x);
 }
 
-// One workgroup: lane l adds slots l, l + 256, ...; the 256 sums are combined in lane order.  a = sum, b = normaliser.
+// One workgroup: slot_total.  a = sum, b = normaliser.
 //   FIN_SUM: loss = a, scale = 1;  FIN_MEAN: loss = a / (b per), scale = 1 / (b per) (NaN / inf when b == 0, as torch);
 //   FIN_MEAN_OR_ZERO: the same, but loss = scale = 0 when b == 0 (every row ignored).
 __global__ __launch_bounds__(LB) void k_finish(float *__restrict__ acc, int blocks, int mode, double per, float *__restrict__ loss) {
-    __shared__ double red[2][LB];
-    const double *part = pair_slots(acc);
-    double a = 0.0, b = 0.0;
-    for (int g = threadIdx.x; g < blocks; g += LB) { a += part[2 * g]; b += part[2 * g + 1]; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    a = 0.0; b = 0.0;
-    for (int t = 0; t < LB; ++t) { a += red[0][t]; b += red[1][t]; }
+    double t[2];
+    if (!slot_total<LB>(pair_slots(acc), blocks, t)) return;
+    const double a = t[0], b = t[1];
     const bool zero = mode == FIN_MEAN_OR_ZERO && !(b > 0.0);
     const double denom = b * per;
     const double scale = mode == FIN_SUM ? 1.0 : zero ? 0.0 : 1.0 / denom;
@@ -87,7 +59,7 @@ __global__ __launch_bounds__(LB) void k_cex_fwd(long n, int c, const float *__re
         const long t = target[r];
         float m = -__builtin_huge_valf();
         for (int j = j0; j < c; j += js) m = fmaxf(m, x[j]);
-        if (WV) m = wave_max_f32(m);
+        if (WV) m = pdf_wave_max_f32(m);
         float s = 0.f;
         for (int j = j0; j < c; j += js) s += expf(x[j] - m);
         if (WV) s = pdf_wave_sum_f32(s);
@@ -128,8 +100,7 @@ __global__ __launch_bounds__(LB) void k_cex_fwd(long n, int c, const float *__re
 // out = d * gy[0] * acc[2]
 __global__ __launch_bounds__(LB) void k_scale(long total, const float *__restrict__ d, const float *__restrict__ acc,
                                               const float *__restrict__ gy, float *__restrict__ out) {
-    const float scale = gy[0] * acc[2];
-    for (long e = (long)blockIdx.x * LB + threadIdx.x; e < total; e += (long)gridDim.x * LB) out[e] = d[e] * scale;
+    pdf_scaled_copy<LB>(total, d, gy[0] * acc[2], out);
 }
 
 // out[r, j] = d[r, j] * gy[r]
@@ -220,7 +191,7 @@ __global__ __launch_bounds__(LB) void k_dice_prob(long n, int c, const float *__
         const float *x = logits + r * c;
         float m = -__builtin_huge_valf();
         for (int j = j0; j < c; j += js) m = fmaxf(m, x[j]);
-        if (WV) m = wave_max_f32(m);
+        if (WV) m = pdf_wave_max_f32(m);
         float s = 0.f;
         for (int j = j0; j < c; j += js) s += expf(x[j] - m);
         if (WV) s = pdf_wave_sum_f32(s);
@@ -262,7 +233,6 @@ __global__ __launch_bounds__(LB) void k_dice_colsum(long n, int c, const float *
 
 __global__ __launch_bounds__(LB) void k_dice_finish(int c, int blocks, const float *__restrict__ slab, float smooth, float exponent,
                                                     long ignore, float *__restrict__ acc, float *__restrict__ loss) {
-    __shared__ double red[LB];
     float *ca = acc + HEAD, *cb = ca + c;
     double terms = 0.0;
     for (int j = threadIdx.x; j < c; j += LB) {
@@ -277,12 +247,10 @@ __global__ __launch_bounds__(LB) void k_dice_finish(int c, int blocks, const flo
         ca[j] = skip ? 0.f : (float)(-2.0 / (den * c));
         cb[j] = skip ? 0.f : (float)((double)exponent * num / (den * den * c));
     }
-    red[threadIdx.x] = terms;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double total = 0.0;
-    for (int t = 0; t < LB; ++t) total += red[t];
-    const float l = (float)(total / c);
+    const double mine[1] = {terms};
+    double total[1];
+    if (!block_sum_by_lanes<LB>(mine, total)) return;   // (the lanes' class terms in lane order)
+    const float l = (float)(total[0] / c);
     acc[0] = l; acc[1] = 0.f; acc[2] = 1.f; acc[3] = 0.f;
     loss[0] = l;
 }

@@ -4,11 +4,11 @@
 //   loss = sum_rows sum_j (xlogy(t_j, t_j) - t_j logp_j) / N       (F.kl_div(..., "batchmean"): the divisor is ALL N rows).
 // The reference builds the target with a boolean-mask assignment (a nonzero: host sync) and ~10 torch kernels; here it is one
 // launch per row block + one fixed-order sum per direction, nothing read back to the host, so the step stays capturable.
-// Shape of csrc/loss.hip: one lane owns one row (Cs <= 64 logits and the target row in registers), the workgroup's partial sum goes
-// to its own slot, one workgroup adds the slots in a fixed order (no float atomics: the loss is bit-reproducible).  The forward leaves
-// the row gradient  softmax(pred / T_p) * sum_j t_j - t  in `grad`; the backward scales it by gy / (T_p N) and only READS it.
+// One lane owns one row (Cs <= 64 logits and the target row in registers); the workgroup's sum goes by waves to its own slot and one
+// workgroup totals the slots (slot_sum.h).  The forward leaves the row gradient  softmax(pred / T_p) * sum_j t_j - t  in `grad`; the
+// backward scales it by gy / (T_p N) and only READS it.
 // Bound: HBM ((Cs + Ct) * 4 + 8 bytes read, Cs * 4 written per row).
-#include "pdfops_common.h"
+#include "slot_sum.h"
 
 namespace {
 
@@ -20,7 +20,6 @@ template <int W>
 __global__ __launch_bounds__(LB) void k_kl_fwd(long n, int cs, int ct, const float *__restrict__ student, const float *__restrict__ teacher,
                                                const long *__restrict__ labels, long ignore, float inv_tp, float inv_tt,
                                                float *__restrict__ grad, float *__restrict__ acc) {
-    __shared__ float red[LB / 64];
     float loss = 0.f;
     for (long r = (long)blockIdx.x * LB + threadIdx.x; r < n; r += (long)gridDim.x * LB) {
         const float *x = student + r * cs;
@@ -81,39 +80,26 @@ __global__ __launch_bounds__(LB) void k_kl_fwd(long n, int cs, int ct, const flo
         for (int j = 0; j < W; ++j)
             if (j < cs) g[j] = __expf(a[j] - m) * is * tsum - t[j];
     }
-    loss = pdf_wave_sum_f32(loss);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {   // the workgroup's sum goes to its own slot: k_kl_mean adds the slots in a fixed order (no float atomics)
-        float v = 0.f;
-        for (int w = 0; w < LB / 64; ++w) v += red[w];
-        acc[PDF_KL_HEAD + blockIdx.x] = v;
-    }
+    float v[1] = {loss};
+    block_sum_by_waves<LB>(v, acc + PDF_KL_HEAD + blockIdx.x);   // the workgroup's own slot
 }
 
 // acc[PDF_KL_HEAD + g] = the workgroups' sums -> acc[0] = total, acc[1] = 1 / (T_p N) (the backward's scale), out = total / N.
-// One workgroup; lane l adds workgroups l, l + 256, ...; the 256 partial sums are combined in lane order.
+// One workgroup: slot_total.
 __global__ __launch_bounds__(LB) void k_kl_mean(float *__restrict__ acc, int blocks, long n, float inv_tp, float *__restrict__ out) {
-    __shared__ float red[LB];
-    float a = 0.f;
-    for (int g = threadIdx.x; g < blocks; g += LB) a += acc[PDF_KL_HEAD + g];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    a = 0.f;
-    for (int t = 0; t < LB; ++t) a += red[t];
+    float t[1];
+    if (!slot_total<LB>(acc + PDF_KL_HEAD, blocks, t)) return;
     const float inv_n = 1.f / (float)n;
-    acc[0] = a;
+    acc[0] = t[0];
     acc[1] = inv_tp * inv_n;
-    out[0] = a * inv_n;
+    out[0] = t[0] * inv_n;
 }
 
 // grad_pred = dgrad * gy / (T_p N).  The forward's buffer is only READ: a second backward over the same graph (retain_graph) sees
 // the unscaled values again.
 __global__ __launch_bounds__(LB) void k_kl_bwd(long total, const float *__restrict__ dgrad, const float *__restrict__ acc,
                                                const float *__restrict__ gy, float *__restrict__ out) {
-    const float scale = gy[0] * acc[1];
-    for (long e = (long)blockIdx.x * LB + threadIdx.x; e < total; e += (long)gridDim.x * LB) out[e] = dgrad[e] * scale;
+    pdf_scaled_copy<LB>(total, dgrad, gy[0] * acc[1], out);
 }
 
 }  // namespace

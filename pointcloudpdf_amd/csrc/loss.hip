@@ -1,10 +1,10 @@
 // Cross-entropy over (N, C) logits with an ignore label, mean over the counted rows -- nn.CrossEntropyLoss as configured on
 // this path (losses/misc.py:14-39: weight=None, label_smoothing=0, reduction="mean", ignore_index=-1).
 // torch runs log_softmax + an nll reduction that is a single-block kernel (173 us forward + 147 us backward for 200k x 13);
-// here one lane owns one row (C <= 64 logits in registers): max / log-sum-exp / picked logit, a block reduction into the block's own
-// slot and a one-workgroup sum over the slots (sum of losses, number of counted rows; fixed order, no atomics).  The forward also leaves softmax - onehot (zero on ignored rows) in
+// here one lane owns one row (C <= 64 logits in registers): max / log-sum-exp / picked logit, the block's [sum of losses | counted rows] by
+// waves into its own slot and a one-workgroup total of the slots (slot_sum.h).  The forward also leaves softmax - onehot (zero on ignored rows) in
 // `grad`, so the backward is one scaled copy.  Bound: HBM (8NC bytes forward).
-#include "pdfops_common.h"
+#include "slot_sum.h"
 #include "vote_row.h"
 
 namespace {
@@ -14,7 +14,6 @@ constexpr int PDF_CE_HEAD = 4, PDF_CE_MAX_BLOCKS = 1024;   // acc = [sum, count,
 
 __global__ __launch_bounds__(LB) void k_ce_fwd(long n, int c, const float *__restrict__ logits, const long *__restrict__ target,
                                                long ignore, float *__restrict__ grad, float *__restrict__ acc) {
-    __shared__ float red[2][LB / 64];
     float loss = 0.f, cnt = 0.f;
     for (long r = (long)blockIdx.x * LB + threadIdx.x; r < n; r += (long)gridDim.x * LB) {
         const float *x = logits + r * c;
@@ -33,39 +32,24 @@ __global__ __launch_bounds__(LB) void k_ce_fwd(long n, int c, const float *__res
         const float inv = 1.f / s;
         for (int j = 0; j < c; ++j) g[j] = counted ? __expf(x[j] - m) * inv - (j == t ? 1.f : 0.f) : 0.f;
     }
-    loss = pdf_wave_sum_f32(loss);
-    cnt = pdf_wave_sum_f32(cnt);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = loss; red[1][threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {   // the block's [sum | count] goes to its own slot: k_ce_mean adds the slots in a fixed order (no float atomics)
-        float a = 0.f, b = 0.f;
-        for (int w = 0; w < LB / 64; ++w) { a += red[0][w]; b += red[1][w]; }
-        acc[PDF_CE_HEAD + 2 * blockIdx.x] = a;
-        acc[PDF_CE_HEAD + 2 * blockIdx.x + 1] = b;
-    }
+    float v[2] = {loss, cnt};
+    block_sum_by_waves<LB>(v, acc + PDF_CE_HEAD + 2 * blockIdx.x);   // the block's own slot
 }
 
 // acc[PDF_CE_HEAD + 2 g] = the blocks' [sum of losses, counted rows] -> acc[0..1] = their totals, out = mean loss (NaN when nothing is
-// counted, as torch).  One workgroup; lane l adds blocks l, l + 256, ...; the 256 partial sums are combined in lane order.
+// counted, as torch).  One workgroup: slot_total.
 __global__ __launch_bounds__(LB) void k_ce_mean(float *__restrict__ acc, int blocks, float *__restrict__ out) {
-    __shared__ float red[2][LB];
-    float a = 0.f, b = 0.f;
-    for (int g = threadIdx.x; g < blocks; g += LB) { a += acc[PDF_CE_HEAD + 2 * g]; b += acc[PDF_CE_HEAD + 2 * g + 1]; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    a = 0.f; b = 0.f;
-    for (int t = 0; t < LB; ++t) { a += red[0][t]; b += red[1][t]; }
-    acc[0] = a; acc[1] = b;
-    out[0] = a / b;
+    float t[2];
+    if (!slot_total<LB>(acc + PDF_CE_HEAD, blocks, t)) return;
+    acc[0] = t[0]; acc[1] = t[1];
+    out[0] = t[0] / t[1];
 }
 
 // grad_logits = (softmax - onehot) * gy / count.  The forward's buffer is only READ: a second backward over the same graph
 // (retain_graph, torch.autograd.grad followed by backward) must see the unscaled values again.
 __global__ __launch_bounds__(LB) void k_ce_bwd(long total, const float *__restrict__ dlogits, const float *__restrict__ acc,
                                                const float *__restrict__ gy, float *__restrict__ out) {
-    const float scale = gy[0] / acc[1];
-    for (long e = (long)blockIdx.x * LB + threadIdx.x; e < total; e += (long)gridDim.x * LB) out[e] = dlogits[e] * scale;
+    pdf_scaled_copy<LB>(total, dlogits, gy[0] / acc[1], out);
 }
 
 // Test-time fragment voting (engines/test.py:218-229, 243-251): pred[index[r], :] += softmax(logits[r, :]) and the running

@@ -21,6 +21,7 @@
 // An element with key 0xFFFFFFFF is an ignored row or has e == 0: it contributes nothing either way, so the two may share the key
 // (ignored rows are background, and every element with e > 0 sorts before them: no count that matters sees them).
 // Bound: HBM (the sort moves 16 NC bytes per pass, four passes).
+#include "slot_sum.h"
 #include "tile_sort.h"
 
 namespace {
@@ -71,21 +72,14 @@ __global__ __launch_bounds__(LB) void k_lv_keys(long n, int c, const float *__re
 
 // fgcnt[cls * ntiles + tile] = foreground elements among the tile's sorted positions
 __global__ __launch_bounds__(LB) void k_lv_fgcount(long n, int ntiles, const unsigned *__restrict__ vals, unsigned *__restrict__ fgcnt) {
-    __shared__ unsigned red[WAVES];
     const int tile = blockIdx.x, cls = blockIdx.y;
     const unsigned *v = vals + (size_t)cls * n;
-    unsigned cntv = 0u;
+    unsigned cntv[1] = {0u}, a[1];
     for (int i = 0; i < ITEMS; ++i) {
         const size_t p = (size_t)tile * TILE + i * LB + threadIdx.x;
-        cntv += (unsigned)__popcll(__ballot(p < (size_t)n && (v[p] >> 31)));   // (wave-uniform)
+        cntv[0] += (unsigned)__popcll(__ballot(p < (size_t)n && (v[p] >> 31)));   // (wave-uniform: already the wave's total)
     }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cntv;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned a = 0u;
-        for (int i = 0; i < WAVES; ++i) a += red[i];
-        fgcnt[(size_t)cls * ntiles + tile] = a;
-    }
+    if (block_sum_wave_totals<LB>(cntv, a)) fgcnt[(size_t)cls * ntiles + tile] = a[0];
 }
 
 // a class is averaged when it occurs among the kept rows and the caller's mask (class_seen) admits it
@@ -97,7 +91,6 @@ __global__ __launch_bounds__(LB) void k_lv_grad(long n, int c, int ntiles, const
                                                 const unsigned *__restrict__ fgoff, const unsigned *__restrict__ total,
                                                 const unsigned char *__restrict__ mask, float *__restrict__ dprob, double *__restrict__ part) {
     __shared__ unsigned wtot[WAVES];
-    __shared__ double red[WAVES];
     const int tile = blockIdx.x, cls = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const size_t seg = (size_t)cls * n;
     const int ncls = __popcll(__ballot(lv_included(lane, c, total, mask)));
@@ -120,7 +113,7 @@ __global__ __launch_bounds__(LB) void k_lv_grad(long n, int c, int ntiles, const
     for (int i = 0; i < w; ++i) run += wtot[i];
     const double g = (double)total[cls], inv_ncls = inc ? 1.0 / (double)ncls : 0.0;
     const unsigned long long upto = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull;
-    double acc = 0.0;
+    double acc[1] = {0.0};
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
         const size_t p = pos(tile, w, r, lane);
@@ -132,27 +125,17 @@ __global__ __launch_bounds__(LB) void k_lv_grad(long n, int c, int ntiles, const
         if (inc && key[r] != LAST_KEY) {   // (an absent class has g == 0: never divided by)
             const double i_ = g - f, u = g + (double)(p + 1) - f;
             const double gr = fg ? 1.0 / u : i_ / (u * (u - 1.0));
-            acc += (double)__uint_as_float(~key[r]) * gr;
+            acc[0] += (double)__uint_as_float(~key[r]) * gr;
             out = (float)((fg ? -gr : gr) * inv_ncls);
         }
         dprob[(size_t)(val[r] & 0x7FFFFFFFu) * c + cls] = out;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) red[w] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int i = 0; i < WAVES; ++i) a += red[i];
-        part[(size_t)cls * ntiles + tile] = a;
-    }
+    block_sum_by_waves<LB>(acc, part + (size_t)cls * ntiles + tile);
 }
 
-// out = [loss, number of classes averaged].  One workgroup; per class lane l adds tiles l, l + 256, ..., the 256 partial sums are combined
-// in lane order, the classes in ascending order.
+// out = [loss, number of classes averaged].  One workgroup; per class the slot_total of its tiles, the classes in ascending order.
 __global__ __launch_bounds__(LB) void k_lv_loss(int c, int ntiles, const double *__restrict__ part, const unsigned *__restrict__ total,
                                                 const unsigned char *__restrict__ mask, const unsigned *__restrict__ bad, float *__restrict__ out) {
-    __shared__ double red[LB];
     int anybad = 0;
     for (int t = threadIdx.x; t < ntiles; t += LB) anybad |= bad[t] != 0u;
     anybad = __syncthreads_or(anybad);
@@ -160,16 +143,8 @@ __global__ __launch_bounds__(LB) void k_lv_loss(int c, int ntiles, const double 
     int ncls = 0;
     for (int j = 0; j < c; ++j) {
         if (!lv_included(j, c, total, mask)) continue;   // (workgroup-uniform)
-        double a = 0.0;
-        for (int t = threadIdx.x; t < ntiles; t += LB) a += part[(size_t)j * ntiles + t];
-        __syncthreads();
-        red[threadIdx.x] = a;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double b = 0.0;
-            for (int t = 0; t < LB; ++t) b += red[t];
-            loss += b;
-        }
+        double b[1];
+        if (slot_total<LB>(part + (size_t)j * ntiles, ntiles, b)) loss += b[0];
         ++ncls;
     }
     if (threadIdx.x != 0) return;
@@ -194,11 +169,9 @@ __global__ __launch_bounds__(LB) void k_lv_softmax_bwd(long n, int c, const floa
 }
 
 // grad_out = dlogits * gy * scale.  The forward's buffer is only READ (retain_graph: a second backward sees the same values).
-// (k_ce_bwd of loss.hip takes its scale from the counted rows in its own workspace; here the scale is an argument: not shared.)
 __global__ __launch_bounds__(LB) void k_lv_bwd(long total, const float *__restrict__ dlogits, const float *__restrict__ gy, float scale,
                                                float *__restrict__ out) {
-    const float s = gy[0] * scale;
-    for (long e = (long)blockIdx.x * LB + threadIdx.x; e < total; e += (long)gridDim.x * LB) out[e] = dlogits[e] * s;
+    pdf_scaled_copy<LB>(total, dlogits, gy[0] * scale, out);
 }
 
 struct LvWorkspace {

@@ -24,6 +24,7 @@
 //                 n below ~1.3e8 whatever the labels; one rounding each for operands beyond), n_pos, n_neg.
 // Only (tp, fp) at group ends enter the areas, so the order inside a tie group is free and the payload is one bit.
 // Bound: HBM (a pass of the sort moves 14 bytes per key; four passes + 8 bytes per group for the compaction).
+#include "slot_sum.h"
 #include "tile_sort.h"
 
 namespace {
@@ -93,19 +94,13 @@ __global__ __launch_bounds__(LB) void k_om_keys(long n, int c, int k, int ntiles
 // workgroup j < k: class j of the histogram; workgroup k: totals = [n_pos, n_valid, NaN seen], and the whole record when there is no score
 __global__ __launch_bounds__(LB) void k_om_sums(int k, int nrows, const unsigned *__restrict__ part, long long *__restrict__ hist,
                                                 u64 *__restrict__ totals, double *__restrict__ record, int has_score) {
-    __shared__ u64 red[3][LB];
     const int j = blockIdx.x;
-    for (int q = 0; q < 3; ++q) {
+    u64 a[3] = {0ull, 0ull, 0ull}, s[3];
+    for (int q = 0; q < 3; ++q) {   // (the partial rows are column-major 32-bit counts: the lanes' sums are formed here, not by slot_total)
         const int col = j < k ? q * k + j : 3 * k + q;
-        u64 a = 0ull;
-        for (int b = threadIdx.x; b < nrows; b += LB) a += part[(size_t)col * HB + b];
-        red[q][threadIdx.x] = a;
+        for (int b = threadIdx.x; b < nrows; b += LB) a[q] += part[(size_t)col * HB + b];
     }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    u64 s[3] = {0ull, 0ull, 0ull};
-    for (int q = 0; q < 3; ++q)
-        for (int t = 0; t < LB; ++t) s[q] += red[q][t];
+    if (!block_sum_by_lanes<LB>(a, s)) return;
     if (j < k) {
         hist[j] = (long long)s[0];
         hist[k + j] = (long long)(s[1] + s[2] - s[0]);
@@ -125,23 +120,17 @@ __device__ __forceinline__ bool om_is_end(const unsigned *keys, size_t p, long n
 // tcnt[tile] = positives among the tile's sorted positions, tcnt[ntiles + tile] = group ends among them
 __global__ __launch_bounds__(LB) void k_om_ends(long n, int ntiles, const unsigned *__restrict__ keys, const unsigned char *__restrict__ pay,
                                                 unsigned *__restrict__ tcnt) {
-    __shared__ unsigned red[2][WAVES];
     const int tile = blockIdx.x;
-    unsigned np = 0u, ne = 0u;
+    unsigned cnt[2] = {0u, 0u}, t[2];   // [positives, ends]
     for (int i = 0; i < ITEMS; ++i) {
         const size_t p = (size_t)tile * TILE + i * LB + threadIdx.x;
         const bool valid = p < (size_t)n;
-        np += (unsigned)__popcll(__ballot(valid && pay[p] != 0));   // (wave-uniform)
-        ne += (unsigned)__popcll(__ballot(valid && om_is_end(keys, p, n)));
+        cnt[0] += (unsigned)__popcll(__ballot(valid && pay[p] != 0));   // (wave-uniform: already the wave's totals)
+        cnt[1] += (unsigned)__popcll(__ballot(valid && om_is_end(keys, p, n)));
     }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = np; red[1][threadIdx.x >> 6] = ne; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned a = 0u, b = 0u;
-        for (int i = 0; i < WAVES; ++i) { a += red[0][i]; b += red[1][i]; }
-        tcnt[tile] = a;
-        tcnt[(size_t)ntiles + tile] = b;
-    }
+    if (!block_sum_wave_totals<LB>(cnt, t)) return;
+    tcnt[tile] = t[0];
+    tcnt[(size_t)ntiles + tile] = t[1];
 }
 
 // E[rank of the group] = (tp, fp) at the group's end; totals[3] = number of groups.  tcnt / gtot: the scanned counts of k_om_ends (the
@@ -185,48 +174,32 @@ __global__ __launch_bounds__(LB) void k_om_walk(long n, int ntiles, const unsign
 // per workgroup (2048 groups): pa[b] = its share of the average-precision sum, ps[b] = of the integer ROC sum
 __global__ __launch_bounds__(LB) void k_om_area(long n, const uint2 *__restrict__ ends, const u64 *__restrict__ totals, double *__restrict__ pa,
                                                 u64 *__restrict__ ps) {
-    __shared__ double reda[WAVES];
-    __shared__ u64 reds[WAVES];
     const u64 groups = totals[3] < (u64)n ? totals[3] : (u64)n;
     const double n_pos = (double)totals[0];
-    double a = 0.0;
-    u64 s = 0ull;
+    double a[1] = {0.0};
+    u64 s[1] = {0ull};
     for (int i = 0; i < ITEMS; ++i) {
         const u64 g = (u64)blockIdx.x * TILE + i * LB + threadIdx.x;
         if (g >= groups) break;
         const uint2 cur = ends[g], prev = g ? ends[g - 1] : make_uint2(0u, 0u);
         const unsigned dtp = cur.x - prev.x;
-        if (dtp) a += (double)dtp / n_pos * ((double)cur.x / ((double)cur.x + (double)cur.y));   // (a group of ignored rows adds nothing)
-        s += (u64)(cur.y - prev.y) * ((u64)cur.x + (u64)prev.x);
+        if (dtp) a[0] += (double)dtp / n_pos * ((double)cur.x / ((double)cur.x + (double)cur.y));   // (a group of ignored rows adds nothing)
+        s[0] += (u64)(cur.y - prev.y) * ((u64)cur.x + (u64)prev.x);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { a += __shfl_xor(a, o, 64); s += __shfl_xor(s, o, 64); }
-    if ((threadIdx.x & 63) == 0) { reda[threadIdx.x >> 6] = a; reds[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double x = 0.0;
-        u64 y = 0ull;
-        for (int i = 0; i < WAVES; ++i) { x += reda[i]; y += reds[i]; }
-        pa[blockIdx.x] = x;
-        ps[blockIdx.x] = y;
-    }
+    block_sum_by_waves<LB>(a, pa + blockIdx.x);   // (two element types: one call each)
+    block_sum_by_waves<LB>(s, ps + blockIdx.x);
 }
 
-// record = [aupr, auroc, n_pos, n_neg].  One workgroup: lane l adds the slots l, l + 256, ..., the 256 sums are combined in lane order.
+// record = [aupr, auroc, n_pos, n_neg].  One workgroup: the slot_total of either array.
 __global__ __launch_bounds__(LB) void k_om_final(int ntiles, const double *__restrict__ pa, const u64 *__restrict__ ps,
                                                  const u64 *__restrict__ totals, double *__restrict__ record) {
-    __shared__ double reda[LB];
-    __shared__ u64 reds[LB];
-    double a = 0.0;
-    u64 s = 0ull;
-    for (int t = threadIdx.x; t < ntiles; t += LB) { a += pa[t]; s += ps[t]; }
-    reda[threadIdx.x] = a;
-    reds[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double x = 0.0;
-    u64 y = 0ull;
-    for (int t = 0; t < LB; ++t) { x += reda[t]; y += reds[t]; }
+    double xs[1];
+    u64 ys[1];
+    const bool t0 = slot_total<LB>(pa, ntiles, xs);   // (every thread makes both calls; both are true on thread 0 only)
+    slot_total<LB>(ps, ntiles, ys);
+    if (!t0) return;
+    const double x = xs[0];
+    const u64 y = ys[0];
     const u64 n_pos = totals[0], n_neg = totals[1] - totals[0];
     const bool bad = totals[2] != 0ull;
     const double nan = __builtin_nan("");

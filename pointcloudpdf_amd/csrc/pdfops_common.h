@@ -78,9 +78,17 @@ __device__ __forceinline__ unsigned long long pdf_wave_max_u64(unsigned long lon
     }
     return v;
 }
-__device__ __forceinline__ float pdf_wave_sum_f32(float v) {
+template <typename T>
+__device__ __forceinline__ T pdf_wave_sum(T v) {   // (any type __shfl_xor moves; the integer sums of the metric passes use it directly)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float pdf_wave_sum_f32(float v) { return pdf_wave_sum(v); }
+__device__ __forceinline__ double pdf_wave_sum_f64(double v) { return pdf_wave_sum(v); }
+__device__ __forceinline__ float pdf_wave_max_f32(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
 

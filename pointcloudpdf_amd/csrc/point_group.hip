@@ -20,8 +20,9 @@
 // rank by a prefix over the root flags (= ascending root index = the reference's order), members in ascending index (a stable sort by
 // rank: pdf_serial_sort, driven by the caller).
 // Bias losses (point_group_v1m1_base.py:74-86): per-row terms in the promoted type (fp32, or double with a float64 centroid), masked sums
-// as per-workgroup slots added by one workgroup in a fixed order in double.  Nothing to zero, no host read, no float atomics.
+// as the slot sums of slot_sum.h in double.  Nothing to zero, no host read, no float atomics.
 #include "knn_grid.h"
+#include "slot_sum.h"
 
 namespace pg {
 namespace {
@@ -225,8 +226,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_round(int n, long total, const i
             if ((unsigned)v >= (unsigned)n || label[v] != lab) continue;
             if (ld(L + v) > lu && atomicMin(L + v, lu) > lu) ++low;
         }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) low += __shfl_xor(low, o, 64);
+    low = pdf_wave_sum(low);
     if (lane == 0 && low) atomicAdd(lowered, low);
 }
 
@@ -323,8 +323,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_proposals_fill(int nc, long npts
         if (cls >= 0 && cls < k) sum += (double)prob[o * k + cls];
         if (masks) masks[(size_t)p * npts + o] = 1;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = pdf_wave_sum_f64(sum);
     if (lane == 0) {
         classes[p] = cls;
         scores[p] = (float)(sum / (double)cnt);
@@ -350,12 +349,6 @@ __global__ __launch_bounds__(TB) void k_intersections(long m, long nsrc, int np,
 }
 
 // ---------------------------------------------------------------------------------------------------------------- bias losses
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ float tsqrt(float v) { return sqrtf(v); }
 __device__ __forceinline__ double tsqrt(double v) { return sqrt(v); }
 __device__ __forceinline__ float tabs(float v) { return fabsf(v); }
@@ -368,7 +361,6 @@ template <typename T>
 __global__ __launch_bounds__(TB) void k_bias_fwd(long n, const float *__restrict__ pred, const float *__restrict__ coord, const T *__restrict__ centroid,
                                                  const long long *__restrict__ instance, long long ignore, float *__restrict__ d1,
                                                  float *__restrict__ d2, double *__restrict__ acc) {
-    __shared__ double red[3][TB / 64];
     double s1 = 0.0, s2 = 0.0, cnt = 0.0;
     for (long i = (long)blockIdx.x * TB + threadIdx.x; i < n; i += (long)gridDim.x * TB) {
         const bool on = instance[i] != ignore;
@@ -396,32 +388,17 @@ __global__ __launch_bounds__(TB) void k_bias_fwd(long n, const float *__restrict
             d2[3 * i + a] = on ? (float)(-((double)gu[a] / (double)pden - through_norm)) : 0.f;
         }
     }
-    s1 = wave_sum_f64(s1); s2 = wave_sum_f64(s2); cnt = wave_sum_f64(cnt);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; red[2][threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s1 = 0.0; s2 = 0.0; cnt = 0.0;
-        for (int w = 0; w < TB / 64; ++w) { s1 += red[0][w]; s2 += red[1][w]; cnt += red[2][w]; }
-        double *slot = acc + LOSS_HEAD + 3 * (size_t)blockIdx.x;
-        slot[0] = s1; slot[1] = s2; slot[2] = cnt;
-    }
+    double v[3] = {s1, s2, cnt};
+    block_sum_by_waves<TB>(v, acc + LOSS_HEAD + 3 * (size_t)blockIdx.x);   // the workgroup's own slot
 }
 
-// One workgroup adds the slots in a fixed order.  denominator = fp32(sum(mask) + 1e-8) as torch forms it (a 0-dim fp32 tensor plus a
+// One workgroup totals the slots (slot_sum.h).  denominator = fp32(sum(mask) + 1e-8) as torch forms it (a 0-dim fp32 tensor plus a
 // Python scalar stays fp32, also next to a float64 numerator); loss = {l1, cosine} in T.
 template <typename T>
 __global__ __launch_bounds__(TB) void k_bias_finish(int blocks, double *__restrict__ acc, T *__restrict__ loss) {
-    __shared__ double red[3][TB];
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int g = threadIdx.x; g < blocks; g += TB) {
-        const double *slot = acc + LOSS_HEAD + 3 * (size_t)g;
-        a += slot[0]; b += slot[1]; c += slot[2];
-    }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b; red[2][threadIdx.x] = c;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    a = 0.0; b = 0.0; c = 0.0;
-    for (int t = 0; t < TB; ++t) { a += red[0][t]; b += red[1][t]; c += red[2][t]; }
+    double t[3];
+    if (!slot_total<TB>(acc + LOSS_HEAD, blocks, t)) return;
+    const double a = t[0], b = t[1], c = t[2];
     const float denom = (float)c + 1e-8f;
     acc[0] = 1.0 / (double)denom; acc[1] = a; acc[2] = b; acc[3] = c;
     loss[0] = (T)a / (T)denom;

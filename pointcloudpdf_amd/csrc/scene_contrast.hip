@@ -18,9 +18,9 @@
 //               indices (tile_sort.h) and added in ascending pair order; rows without a pair are written as zeros.
 //
 // Masked reconstruction heads (:274-307).  k_recon_fwd: 32 lanes per row; a masked row forms its three outputs and its loss term, the
-// per-workgroup slots are added by one workgroup in slot order, in double; the denominator is the masked count of the same pass.
+// per-workgroup slots are totalled by one workgroup in double (slot_sum.h); the denominator is the masked count of the same pass.
 // k_recon_bwd writes d feat (zero rows where unmasked) and per-workgroup slabs of d weight | d bias, summed in slab order.
-#include "pdfops_common.h"
+#include "slot_sum.h"
 #include "tile_sort.h"
 
 namespace msc {
@@ -220,9 +220,8 @@ __global__ __launch_bounds__(TB) void k_fwd(FwdArgs a) {
     }
 }
 
-// one workgroup: lse per row, the three means in double (lane-strided rows, then the lanes in order)
+// one workgroup: lse per row, the three means in double (lane-strided rows, then by lanes: slot_sum.h)
 __global__ __launch_bounds__(TB) void k_fwd_fin(FwdArgs a, float *__restrict__ lse, float *__restrict__ out) {
-    __shared__ double red[3][TB];
     double s_loss = 0.0, s_pos = 0.0, s_all = 0.0;
     for (long i = threadIdx.x; i < a.p; i += TB) {
         float m = -INFINITY;
@@ -239,16 +238,13 @@ __global__ __launch_bounds__(TB) void k_fwd_fin(FwdArgs a, float *__restrict__ l
         s_pos += (double)d;
         s_all += (double)rs / (double)a.p;
     }
-    red[0][threadIdx.x] = s_loss; red[1][threadIdx.x] = s_pos; red[2][threadIdx.x] = s_all;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double x = 0.0, y = 0.0, w = 0.0;
-        for (int k = 0; k < TB; ++k) { x += red[0][k]; y += red[1][k]; w += red[2][k]; }
-        const double p = (double)a.p;
-        out[0] = (float)(x / p);
-        out[1] = (float)(y / p);
-        out[2] = (float)(w / p - (y / p) / p);
-    }
+    const double v[3] = {s_loss, s_pos, s_all};
+    double t[3];
+    if (!block_sum_by_lanes<TB>(v, t)) return;
+    const double p = (double)a.p;
+    out[0] = (float)(t[0] / p);
+    out[1] = (float)(t[1] / p);
+    out[2] = (float)(t[2] / p - (t[1] / p) / p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -482,18 +478,11 @@ __global__ __launch_bounds__(TB) void k_recon_fwd(ReconArgs a) {
 }
 
 __global__ __launch_bounds__(TB) void k_recon_fwd_fin(int slots, double *__restrict__ acc, float *__restrict__ loss) {
-    __shared__ double red[2][TB];
-    double s = 0.0, n = 0.0;
-    for (int k = threadIdx.x; k < slots; k += TB) { s += acc[ACC_HEAD + 2 * k]; n += acc[ACC_HEAD + 2 * k + 1]; }
-    red[0][threadIdx.x] = s; red[1][threadIdx.x] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double x = 0.0, y = 0.0;
-        for (int k = 0; k < TB; ++k) { x += red[0][k]; y += red[1][k]; }
-        loss[0] = (float)(x / y);               // 0 / 0 = NaN without a masked row, as upstream
-        acc[0] = y > 0.0 ? 1.0 / y : 0.0;
-        acc[1] = y;
-    }
+    double t[2];   // [sum of terms, masked rows]
+    if (!slot_total<TB>(acc + ACC_HEAD, slots, t)) return;
+    loss[0] = (float)(t[0] / t[1]);             // 0 / 0 = NaN without a masked row, as upstream
+    acc[0] = t[1] > 0.0 ? 1.0 / t[1] : 0.0;
+    acc[1] = t[1];
 }
 
 __global__ __launch_bounds__(TB) void k_recon_bwd(ReconArgs a) {
