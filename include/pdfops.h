@@ -58,8 +58,10 @@ extern "C" {
  * 19 = pdf_transition_up_* and the two-problem entries pdf_bn_coef_from_partial2 / pdf_bn_act_backward2 / pdf_rowlin_wgrad2 added (no
  *      existing parameter list changed);
  * 20 = pdf_rowlin_forward_stats2 / pdf_rowlin_dgrad2 / pdf_rowlin_wgrad2_paired added (no existing parameter list changed);
- * 21 = pdf_msc_* added (no existing parameter list changed). */
-#define PDF_ABI_VERSION 21
+ * 21 = pdf_msc_* added (no existing parameter list changed);
+ * 22 = pdf_rowlin_wgrad_group_dgrad / pdf_rowlin_wgrad2_roww added; pdf_td_fwd_scratch_floats is the SUM of its two workspaces, which pdf_td_forward now uses side
+ *      by side (no existing parameter list changed). */
+#define PDF_ABI_VERSION 22
 int pdf_abi_version(void);
 const char *pdf_build_info(void);
 /* Arithmetic of the squared distance in this library's geometry kernels (kNN, ball query, FPS): 0 = the reference's expression as
@@ -293,6 +295,17 @@ int pdf_rowlin_wgrad_multi(long n, int k, int o, int ng, const float *const *g, 
 int pdf_rowlin_wgrad_group(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx,
                            const float *const *scale, const float *const *shift, const int *relu, float *const *dw,
                            float *const *db, float *ws, int mma_input, void *stream);
+/* pdf_rowlin_wgrad_group and the independent input gradient gx (n, k) (+)= dy (n, o) W (W (o, k) row-major, i.e. pdf_rowlin_forward with
+ * transpose_w = 1) over the same rows -- a Bottleneck's five weight gradients beside its gx += dy W1: ONE launch for both + the slab
+ * reduction at the model's widths (k = o in {32, 64} in the slab form, {128, 256, 512} up to 16,384 rows in the group form), the
+ * product's launch followed by pdf_rowlin_wgrad_group otherwise (other shapes or forms, mma_input != 0, PDFOPS_PAIR=0 in the
+ * environment) -- the same bits.  gx must overlap neither an input of the gradients nor ws.  `paired` (nullable) receives 1 when the
+ * product went out in the gradients' launch, 0 when on its own.  PDF_ERR_UNSUPPORTED as pdf_rowlin_wgrad_group: the product has been
+ * issued then, the gradients have not. */
+int pdf_rowlin_wgrad_group_dgrad(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx,
+                                 const float *const *scale, const float *const *shift, const int *relu, float *const *dw,
+                                 float *const *db, float *ws, const float *dy, const float *w, float *gx, int accumulate,
+                                 int *paired, int mma_input, void *stream);
 
 /* Rigid KPConv of the StratifiedTransformer stem (stratified_transformer_v1m1_origin.py:582-662 over torch_points3d's KPConvLayer): the
  * part that is not a matrix product.  weighted[n, k, c] = sum_m max(0, 1 - |support[nb[n, m]] - query[n] - k_points[k]| / extent) *
@@ -362,6 +375,10 @@ int pdf_rowlin_forward_stats2(long n0, int k0, long n1, int k1, int o, void *con
 int pdf_rowlin_dgrad2(long n0, int k0, long n1, int k1, int o, void *const *p, int *paired, int mma_input, void *stream);
 /* pdf_rowlin_wgrad2 with the same report. */
 int pdf_rowlin_wgrad2_paired(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, int *paired, int mma_input, void *stream);
+/* The same with a per-row weight on problem 0's gradient rows, dW_0 = sum_n roww[n] g_0[n]^T x_0[n] (element stride rws; problem 1 of vector
+ * width 2, i.e. o_1 = 32: the two Gram products of pdf_td_forward): one product launch, one each with PDFOPS_PAIR=0 or mma_input != 0. */
+int pdf_rowlin_wgrad2_roww(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, const float *roww, long rws, int *paired,
+                           int mma_input, void *stream);
 
 /* Row-weighted variants of the streaming Linear kernels and the bare BatchNorm-backward sums (building blocks of pdf_td_*). */
 int pdf_rowlin_forward_roww(long n, int k, int o, const float *x, long ldx, const float *w, int transpose_w, float *y, long ldy,

@@ -101,12 +101,14 @@ ENTRIES = {
     "pdf_rowlin_multi": ("s", "liiiiplpipppipliip"),
     "pdf_rowlin_wgrad_multi": ("s", "liiiplplppipppip"),
     "pdf_rowlin_wgrad_group": ("s", "liiiplpl" + "p" * 6 + "ip"),
+    "pdf_rowlin_wgrad_group_dgrad": ("s", "liiiplpl" + "p" * 6 + "pppipip"),
     "pdf_rowlin_dgrad_bstats": ("s", "liiiplpplplpippip"),
     "pdf_rowlin_forward_bn": ("s", "liiplppppiplpppppffpip"),
     "pdf_rowlin_wgrad2": ("s", "liiliipip"),
     "pdf_rowlin_forward_stats2": ("s", "liliippip"),
     "pdf_rowlin_dgrad2": ("s", "liliippip"),
     "pdf_rowlin_wgrad2_paired": ("s", "liiliippip"),
+    "pdf_rowlin_wgrad2_roww": ("s", "liiliipplpip"),
     "pdf_rowlin_forward_roww": ("s", "liiplpipliplip"),
     "pdf_rowlin_wgrad_roww": ("s", "liiplplpplpip"),
     # csrc/kpconv.hip

@@ -28,7 +28,7 @@ def library_path(dist_fma=0):
 
 
 LIB_PATH = library_path(DIST_FMA)
-ABI_VERSION = 21  # include/pdfops.h: PDF_ABI_VERSION (the rows of _abi.ENTRIES are THIS version's parameter lists)
+ABI_VERSION = 22  # include/pdfops.h: PDF_ABI_VERSION (the rows of _abi.ENTRIES are THIS version's parameter lists)
 
 c_int = ctypes.c_int
 c_void_p = ctypes.c_void_p

@@ -64,6 +64,7 @@ static bool dgrad_bstats() {   // PDFOPS_DGRAD_BSTATS=0: BatchNorm-backward sums
 
 // defer_wgrad: the three weight-gradient products (q / k / v, linear1) are left to the caller (pdf_bottleneck_backward issues them together
 // with linear3's in ONE grouped launch); their inputs -- g_xq / g_xk / g_xv, z1 + coef1, dy, x -- stay untouched until then.
+// With defer_wgrad the last product, gx (+)= dy W1, is the caller's as well: it goes out in the grouped launch (pdf_rowlin_wgrad_group_dgrad).
 static int block_pre_backward(long n, int c, void *const *p, int training, int accumulate_gx, int mma_input, void *stream, bool defer_wgrad = false) {
     if (n < 1 || !p || !p[14]) return PDF_ERR_BAD_ARG;
     const float *x = (const float *)p[0], *z1 = (const float *)p[1], *coef1 = (const float *)p[2], *W1 = (const float *)p[3];
@@ -88,7 +89,7 @@ static int block_pre_backward(long n, int c, void *const *p, int training, int a
         e << pdf_bn_act_backward_presummed(n, c, dy, z1, coef1, training, 1, partial, prow, db1, dy, stream);
     }
     if (!defer_wgrad) e << pdf_rowlin_wgrad(n, c, c, dy, c, x, c, nullptr, nullptr, 0, dW1, nullptr, wslab, mma_input, stream);   // dW1 needs the finished dy (after the q/k/v reduction in stream order)
-    e << pdf_rowlin_forward(n, c, c, dy, c, W1, 1, nullptr, nullptr, nullptr, 0, gx, c, accumulate_gx, nullptr, mma_input, stream);
+    if (!defer_wgrad) e << pdf_rowlin_forward(n, c, c, dy, c, W1, 1, nullptr, nullptr, nullptr, 0, gx, c, accumulate_gx, nullptr, mma_input, stream);
     return e.rc;
 }
 
@@ -237,7 +238,7 @@ extern "C" int pdf_bottleneck_backward(long n, int nsample, int c, void *const *
                                (float *)p[41], (float *)p[42], (const int *)p[43], (const int *)p[44], entry_base,
                                (float *)p[40], (float *)p[32], storage_bf16, (const int *)p[49], (const double *)p[46], stream);
     void *pre[15] = {p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[35], p[36], p[37], p[29], p[30], p[45], p[40], ws_pre};
-    e << block_pre_backward(n, c, pre, training, 1, mma_input, stream, group);   // gx += dy W1 on top of the identity branch
+    e << block_pre_backward(n, c, pre, training, 1, mma_input, stream, group);   // gx += dy W1 on top of the identity branch (group: below)
     if (group && e.rc == 0) {
         const long cc = (long)c * c;
         float *gpre = (float *)p[30], *gpost = (float *)p[31];                  // block_pre_backward / block_post_backward gradient layouts
@@ -249,8 +250,11 @@ extern "C" int pdf_bottleneck_backward(long n, int nsample, int c, void *const *
         const int relu[5] = {1, 1, 1, 1, 0};
         float *dw[5] = {dW3, dqkv, dqkv + (cc + c), dqkv + 2 * (cc + c), dW1};
         float *db[5] = {nullptr, dqkv + cc, dqkv + (cc + c) + cc, dqkv + 2 * (cc + c) + cc, nullptr};
-        const int rc = pdf_rowlin_wgrad_group(n, c, c, 5, g, c, x, c, sc, sh, relu, dw, db, ws_post, mma_input, stream);
-        if (rc == PDF_ERR_UNSUPPORTED) {   // widths outside the streaming kernels: one product at a time
+        // gx += dy W1 (reads dy and W1, reads and writes gx -- none of them an input of the gradients, which write only their workspace) shares
+        // the gradients' launch: one node instead of two, and at levels 3-5 most of the product runs beside the longer gradients
+        const int rc = pdf_rowlin_wgrad_group_dgrad(n, c, c, 5, g, c, x, c, sc, sh, relu, dw, db, ws_post, (const float *)p[45], (const float *)p[4],
+                                                    (float *)p[29], 1, nullptr, mma_input, stream);
+        if (rc == PDF_ERR_UNSUPPORTED) {   // widths outside the streaming kernels: one product at a time (gx += dy W1 has been issued)
             e << pdf_rowlin_wgrad(n, c, c, g[0], c, x[0], c, sc[0], sh[0], 1, dw[0], nullptr, ws_post, mma_input, stream);
             e << pdf_rowlin_wgrad_multi(n, c, c, 3, g + 1, c, x[1], c, sc[1], sh[1], 1, dw + 1, db + 1, ws_pre, mma_input, stream);
             e << pdf_rowlin_wgrad(n, c, c, g[4], c, x[4], c, nullptr, nullptr, 0, dw[4], nullptr, ws_pre, mma_input, stream);

@@ -193,10 +193,12 @@ int pdf_bn_finalize2(PdfBnFinalize2 q, float eps, float momentum, void *stream);
 int pdf_bn_backward2(PdfBnBwd2 q, int relu, void *stream);                         // pointwise.hip: reduce -> column sums -> apply, 3 launches
 // rowlin.hip: the two weight-gradient products (rl2::k_wg2: one launch, own workspace each) followed by ONE two-problem slab reduction.
 // Streaming shapes only (PDF_ERR_UNSUPPORTED otherwise).  ws[i]: pdf_rowlin_wgrad_ws_floats(n[i], k[i], o[i], 1) floats; db[i] may be null.
+// roww (nullable, element stride rws): a per-row weight of problem 0's gradient rows, dW_0 = sum_n roww[n] g_0[n]^T x_0[n] (rl2::k_wg2_roww).
 struct PdfWgrad2 {
     long n[2]; int k[2], o[2];
     const float *g[2], *x[2];
     float *dw[2], *db[2], *ws[2];
+    const float *roww = nullptr; long rws = 0;
 };
 int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream, int *paired = nullptr);   // paired: 1 = the products went out as one launch
 // rowlin.hip: the two input gradients gx_i (n_i, k_i) = g_i (n_i, o) W_i of Linear layers with one output width o, as one launch where the

@@ -346,7 +346,8 @@ extern "C" int pdf_rowlin_wgrad(long n, int k, int o, const float *g, long ldg, 
 }
 
 // Two weight gradients of different shapes: the products of pdf_rowlin_wgrad (rl2::wg_block, each problem with its own row split and
-// workspace) as ONE launch where both take the same vector width (rl2::k_wg2; PDFOPS_PAIR=0 or unequal widths: one launch each), then
+// workspace) as ONE launch where both take the same vector width (rl2::k_wg2; PDFOPS_PAIR=0 or unequal widths: one launch each) or where
+// problem 0 carries a row weight (q.roww: rl2::k_wg2_roww, the two Gram products of a TransitionDown forward), then
 // ONE launch that reduces the slabs of both (rl2::k_slab_reduce2: each problem with the grid and the lane count of its own reduction --
 // the same sums in the same order).  Two launches instead of four.  Validates everything before the first launch.  paired (nullable): receives
 // 1 when the two products went out as one launch, 0 when as two.
@@ -361,6 +362,7 @@ int pdf_rowlin_wgrad_pair(const PdfWgrad2 &q, int mma_input, void *stream, int *
         p[i] = wgrad_shape(q.n[i], q.k[i], q.o[i], q.o[i], q.k[i], q.ws[i]);
         p[i].g[0] = q.g[i]; p[i].x = q.x[i]; p[i].dw[0] = q.dw[i]; p[i].db[0] = q.db[i];
     }
+    p[0].roww = q.roww; p[0].rws = q.rws;
     hipStream_t s = static_cast<hipStream_t>(stream);
     rl2::RArgs r[2] = {};
     const int took = rl2::try_wgrad_pair(p, pdf_pair_launches(), mma_input, s, r);
@@ -448,6 +450,19 @@ extern "C" int pdf_rowlin_wgrad2_paired(long n0, int k0, int o0, long n1, int k1
     if (!p) return PDF_ERR_BAD_ARG;
     PdfWgrad2 q;
     q.n[0] = n0; q.k[0] = k0; q.o[0] = o0; q.n[1] = n1; q.k[1] = k1; q.o[1] = o1;
+    for (int i = 0; i < 2; ++i) {
+        void *const *t = p + 5 * i;
+        q.g[i] = (const float *)t[0]; q.x[i] = (const float *)t[1]; q.dw[i] = (float *)t[2]; q.db[i] = (float *)t[3]; q.ws[i] = (float *)t[4];
+    }
+    return pdf_rowlin_wgrad_pair(q, mma_input, stream, paired);
+}
+// pdf_rowlin_wgrad2_paired with a per-row weight on problem 0's gradient rows (dW_0 = sum_n roww[n] g_0[n]^T x_0[n], element stride rws):
+// the two Gram products of pdf_td_forward.  Same table; *paired: 1 when the two products went out as one launch (rl2::k_wg2_roww).
+extern "C" int pdf_rowlin_wgrad2_roww(long n0, int k0, int o0, long n1, int k1, int o1, void *const *p, const float *roww, long rws, int *paired,
+                                      int mma_input, void *stream) {
+    if (!p || !roww) return PDF_ERR_BAD_ARG;
+    PdfWgrad2 q;
+    q.n[0] = n0; q.k[0] = k0; q.o[0] = o0; q.n[1] = n1; q.k[1] = k1; q.o[1] = o1; q.roww = roww; q.rws = rws;
     for (int i = 0; i < 2; ++i) {
         void *const *t = p + 5 * i;
         q.g[i] = (const float *)t[0]; q.x[i] = (const float *)t[1]; q.dw[i] = (float *)t[2]; q.db[i] = (float *)t[3]; q.ws[i] = (float *)t[4];
@@ -544,6 +559,39 @@ extern "C" int pdf_rowlin_wgrad_group(long n, int k, int o, int ng, const float 
     }
     if (!rl2::try_wgrad(p, mma_input, static_cast<hipStream_t>(stream))) return PDF_ERR_UNSUPPORTED;
     return pdf_launch_status();
+}
+
+// pdf_rowlin_wgrad_group and the independent input gradient gx (n, k) (+)= dy (n, o) W (W (o, k) row-major: pdf_rowlin_forward with
+// transpose_w = 1) of the same rows: a Bottleneck's five weight gradients and its gx += dy W1.  ONE launch for both (rl2::k_wg_fwd) + the
+// slab reduction where the shapes are the paired ones (fp32 operands; rl2::try_wgrad_fwd), else -- and with PDFOPS_PAIR=0 -- the product's
+// launch, then pdf_rowlin_wgrad_group: the same bits.  gx must not overlap anything the gradients read, nor ws.  Validates everything
+// before the first launch.  PDF_ERR_UNSUPPORTED as pdf_rowlin_wgrad_group: the product HAS been issued then, the weight gradients have not.
+// paired (nullable): receives 1 when the product went out in the gradients' launch, 0 when on its own.
+extern "C" int pdf_rowlin_wgrad_group_dgrad(long n, int k, int o, int ng, const float *const *g, long ldg, const float *const *x, long ldx,
+                                            const float *const *scale, const float *const *shift, const int *relu, float *const *dw,
+                                            float *const *db, float *ws, const float *dy, const float *w, float *gx, int accumulate,
+                                            int *paired, int mma_input, void *stream) {
+    if (paired) *paired = 0;
+    if (!rl2::mma_input_ok(mma_input)) return PDF_ERR_BAD_ARG;
+    if (n < 1 || k < 1 || o < 1 || ng < 1 || ng > rl2::WG_MAXG || !g || !x || !scale || !shift || !relu || !dw || !ws || !dy || !w || !gx) return PDF_ERR_BAD_ARG;
+    for (int i = 0; i < ng; ++i) if (!g[i] || !x[i] || !dw[i] || (scale[i] && !shift[i])) return PDF_ERR_BAD_ARG;
+    if (pdf_pair_launches() && rowlin_streams(k, o) && rowlin_streams(o, k)) {
+        rl2::Wgrad p = wgrad_shape(n, k, o, ldg, ldx, ws);
+        p.ng = ng; p.per_gradient = true;
+        for (int i = 0; i < ng; ++i) {
+            p.g[i] = g[i]; p.xz[i] = x[i]; p.scalez[i] = scale[i]; p.shiftz[i] = shift[i]; p.reluz[i] = relu[i];
+            p.dw[i] = dw[i]; p.db[i] = db ? db[i] : nullptr;
+        }
+        rl2::Forward f = forward1(n, o, k, dy, o, w, 1, gx, k);   // (the product reduces over o and is k wide)
+        f.accumulate = accumulate;
+        if (rl2::try_wgrad_fwd(p, f, mma_input, static_cast<hipStream_t>(stream))) {
+            if (paired) *paired = 1;
+            return pdf_launch_status();
+        }
+    }
+    const int rc = pdf_rowlin_forward(n, o, k, dy, o, w, 1, nullptr, nullptr, nullptr, 0, gx, k, accumulate, nullptr, mma_input, stream);
+    if (rc) return rc;
+    return pdf_rowlin_wgrad_group(n, k, o, ng, g, ldg, x, ldx, scale, shift, relu, dw, db, ws, mma_input, stream);
 }
 
 // Row-weighted variants for the streaming shapes (csrc/transition_down.hip: Gram matrices x^T diag(cnt) x and the dense part of

@@ -64,8 +64,11 @@ int try_forward(const Forward &p, int mma, hipStream_t s, int *partial_rows = nu
 int try_forward2(const Forward (&p)[2], int mma, hipStream_t s);         // plain products of ONE reduction width k (k_fwd2 / k_fwd_group2)
 int try_forward_stats2(const Forward (&p)[2], int mma, hipStream_t s);   // one output width o, statistics epilogue (k_fwd_stats2)
 int try_wgrad(const Wgrad &p, int mma, hipStream_t s);   // the product and its slab reduction
-// Two single, plain weight gradients whose reductions are left to the caller (r[2]: launch_slab_reduce2).  Returns 2: one launch, 1: two.
+// Two single weight gradients without prologue whose reductions are left to the caller (r[2]: launch_slab_reduce2); p[0] may carry a row
+// weight.  Returns 2: one launch, 1: two.
 int try_wgrad_pair(const Wgrad (&p)[2], bool pair, int mma, hipStream_t s, RArgs *r);
+// Grouped weight gradients (per_gradient) + their reduction with ONE plain product in the products' launch (k_wg_fwd): 1, or 0 and nothing launched.
+int try_wgrad_fwd(const Wgrad &w, const Forward &f, int mma, hipStream_t s);
 void launch_slab_reduce(const RArgs &a, int ng, bool any_bias, hipStream_t s);
 void launch_slab_reduce2(const RArgs &a0, bool bias0, const RArgs &a1, bool bias1, hipStream_t s);
 int stats_rows(long n);                  // rows of the statistics epilogue ...

@@ -11,6 +11,7 @@ template int try_wgrad_mp<0>(const Wgrad &, hipStream_t);
 template int try_forward2_mp<0>(const Forward (&)[2], hipStream_t);
 template int try_wgrad_pair_mp<0>(const Wgrad (&)[2], bool, hipStream_t, RArgs *);
 template int try_forward_stats2_mp<0>(const Forward (&)[2], hipStream_t);
+template int try_wgrad_fwd_mp<0>(const Wgrad &, const Forward &, hipStream_t);
 extern template int try_forward_mp<1>(const Forward &, hipStream_t, int *);   // rowlin2_f16.hip
 extern template int try_wgrad_mp<1>(const Wgrad &, hipStream_t);
 extern template int try_wgrad_pair_mp<1>(const Wgrad (&)[2], bool, hipStream_t, RArgs *);
@@ -39,4 +40,5 @@ int try_wgrad_pair(const Wgrad (&p)[2], bool pair, int mma, hipStream_t s, RArgs
 // The paired product kernels are built for fp32 operands only: mma_input 1 / 2 gets 0 here, i.e. two single launches.
 int try_forward2(const Forward (&p)[2], int mma, hipStream_t s) { return mma == 0 ? try_forward2_mp<0>(p, s) : 0; }
 int try_forward_stats2(const Forward (&p)[2], int mma, hipStream_t s) { return mma == 0 ? try_forward_stats2_mp<0>(p, s) : 0; }
+int try_wgrad_fwd(const Wgrad &w, const Forward &f, int mma, hipStream_t s) { return mma == 0 ? try_wgrad_fwd_mp<0>(w, f, s) : 0; }
 }  // namespace rl2

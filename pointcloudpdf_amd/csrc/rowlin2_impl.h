@@ -484,12 +484,16 @@ template <> struct Vec<2> { typedef float type __attribute__((ext_vector_type(2)
 template <> struct Vec<4> { typedef float type __attribute__((ext_vector_type(4))); };
 
 // One workgroup of k_wg: (bx, by, bz) = its block id in the grid of ITS problem, (gdx, gdy) = that grid's extents (block coordinates: as fwd_block).
+// red [4][(16 VW)^2] and redb [4][16 VW] are the workgroup's LDS (wg_lds_floats<VW>() floats, redb behind red): one (16 VW)^2 block per
+// wave -- plain stores, then a 4-way sum (LDS atomics cost 20 us here).  The caller owns them: a single launch passes static arrays, a
+// launch shared with a product that keeps a weight image in dynamic LDS passes that image's bytes (the larger of the two sizes, not the sum).
+template <int VW> constexpr int wg_lds_floats() { return 4 * (16 * VW) * (16 * VW) + 4 * (16 * VW); }
 template <int VW, bool PRE, bool RW, int MP>   // RW: per-row weight of G (a.roww); MP: Mma
-__device__ __forceinline__ void wg_block(const WArgs &a, const unsigned bx, const unsigned by, const unsigned bz, const unsigned gdx, const unsigned gdy) {
+__device__ __forceinline__ void wg_block(const WArgs &a, const unsigned bx, const unsigned by, const unsigned bz, const unsigned gdx, const unsigned gdy,
+                                         float *red, float *redb) {
     typedef typename Vec<VW>::type vec;
     constexpr int B = 16 * VW;   // block edge of dW
-    __shared__ float red[4][B * B];   // one (16 VW)^2 block per wave: plain stores, then a 4-way sum (LDS atomics cost 20 us here)
-    __shared__ float redb[4][B];
+    constexpr int BB = B * B;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, nq = lane >> 4;
     const int nkb = a.K / B;
@@ -579,7 +583,7 @@ __device__ __forceinline__ void wg_block(const WArgs &a, const unsigned bx, cons
 #pragma unroll
         for (int c2 = 0; c2 < VW; ++c2)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) red[wave][(VW * (4 * nq + r) + c) * B + VW * li + c2] = acc[c][c2][r];
+            for (int r = 0; r < 4; ++r) red[wave * BB + (VW * (4 * nq + r) + c) * B + VW * li + c2] = acc[c][c2][r];
     float *db = a.db[bz];
     const bool want_db = db && kb == 0;
     if (want_db) {
@@ -588,19 +592,20 @@ __device__ __forceinline__ void wg_block(const WArgs &a, const unsigned bx, cons
             float g = gsum[c];
             g += __shfl_xor(g, 16, 64);
             g += __shfl_xor(g, 32, 64);
-            if (nq == 0) redb[wave][VW * li + c] = g;
+            if (nq == 0) redb[wave * B + VW * li + c] = g;
         }
     }
     __syncthreads();
     float *slab = a.slab + (((size_t)bz * gdy + by) * gdx + bx) * (B * B);
-    for (int e = threadIdx.x; e < B * B; e += 256) slab[e] = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
+    for (int e = threadIdx.x; e < BB; e += 256) slab[e] = (red[e] + red[BB + e]) + (red[2 * BB + e] + red[3 * BB + e]);
     if (want_db && threadIdx.x < B)
         a.bslab[(((size_t)bz * (a.O / B) + ob / B) * gdx + bx) * B + threadIdx.x] =
-            (redb[0][threadIdx.x] + redb[1][threadIdx.x]) + (redb[2][threadIdx.x] + redb[3][threadIdx.x]);
+            (redb[threadIdx.x] + redb[B + threadIdx.x]) + (redb[2 * B + threadIdx.x] + redb[3 * B + threadIdx.x]);
 }
 template <int VW, bool PRE, bool RW, int MP>
 __global__ __launch_bounds__(256) void k_wg(WArgs a) {
-    wg_block<VW, PRE, RW, MP>(a, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
+    __shared__ float red[wg_lds_floats<VW>()];
+    wg_block<VW, PRE, RW, MP>(a, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, red, red + 4 * (16 * VW) * (16 * VW));
 }
 // Two single-gradient products without prologue or row weight in one launch (the two weight gradients of a TransitionUp join): each
 // problem with its own K, O, row split and workspace; workgroups below `split` are problem 0's grid (x fastest), the rest problem 1's.
@@ -609,7 +614,53 @@ template <int VW, int MP>
 __global__ __launch_bounds__(256) void k_wg2(WArgs2 q) {
     const int i = blockIdx.x >= q.split ? 1 : 0;
     const unsigned b = blockIdx.x - (i ? q.split : 0u), gx = q.gx[i];
-    wg_block<VW, false, false, MP>(q.a[i], b % gx, b / gx, 0u, gx, q.gy[i]);
+    __shared__ float red[wg_lds_floats<VW>()];
+    wg_block<VW, false, false, MP>(q.a[i], b % gx, b / gx, 0u, gx, q.gy[i], red, red + 4 * (16 * VW) * (16 * VW));
+}
+// The same with a vector width per problem and a row weight on problem 0 (the two Gram products of a TransitionDown forward:
+// x^T diag(cnt) x, cin wide, and [R | cnt]^T x, 32 wide).  One LDS block, the larger of the two bodies'.
+template <int VW0, int VW1, int MP>
+__global__ __launch_bounds__(256) void k_wg2_roww(WArgs2 q) {
+    __shared__ float red[wg_lds_floats<(VW0 > VW1 ? VW0 : VW1)>()];
+    if (blockIdx.x < q.split) {
+        const unsigned gx = q.gx[0];
+        wg_block<VW0, false, true, MP>(q.a[0], blockIdx.x % gx, blockIdx.x / gx, 0u, gx, q.gy[0], red, red + 4 * (16 * VW0) * (16 * VW0));
+    } else {
+        const unsigned b = blockIdx.x - q.split, gx = q.gx[1];
+        wg_block<VW1, false, false, MP>(q.a[1], b % gx, b / gx, 0u, gx, q.gy[1], red, red + 4 * (16 * VW1) * (16 * VW1));
+    }
+}
+
+// The grouped weight gradients of a Bottleneck (per-gradient inputs with prologue: k_wg<VW, true, false>) and ONE plain product (one input,
+// one output, no prologue, no statistics: the block's gx += dy W1) in one launch.  The two are independent: the product reads dy and W1
+// and reads / writes gx, the gradients read their inputs and write only the slab workspace.  Workgroups below `split` are the gradients'
+// grid, flattened x fastest, then y, then z -- the longer problem first -- and the rest are the product's grid (x fastest); each runs the
+// body of its single launch over the grid of its single launch: the same slabs and the same product bits.  The LDS of both bodies is ONE
+// dynamic block sized as the larger of the two (wg_block's four dW blocks, the group form's weight image): added together, 66.5 KB + the
+// image would leave one workgroup per CU.
+struct WgFwdArgs { WArgs w; FwdArgs f; unsigned wgx, wgy, split, fgx; };
+// Waves per SIMD asked of the compiler: the group forms as k_fwd_group; the slab forms what keeps the launch within the registers of the
+// wider of its two single kernels.  Left alone (one wave per SIMD allowed) the compiler takes the larger VGPR count of one body plus the
+// larger AGPR count of the other: 52 + 16 at K = 32 against k_fwd<32, 2>'s 50 + 12 and k_wg<2, true, false>'s 39 + 16, 120 + 88 at K = 64
+// against k_fwd<64, 4>'s 118 + 24 and k_wg<4, true, false>'s 84 + 88.  With the bounds below: 58 and 134 registers, no AGPRs, no scratch
+// (the group forms: 123 / 123 / 128; the table of every instantiation: profiles/paired_block_bench.json).
+template <int K, bool GROUP> constexpr int wg_fwd_min_waves() { return GROUP ? 2 : (K == 32 ? 8 : 3); }
+template <int VW, int K, int NB, bool GROUP, int MINW = wg_fwd_min_waves<K, GROUP>()>   // NB: 16-column blocks per wave (slab form) or per workgroup (group form)
+__global__ __launch_bounds__(256, MINW) void k_wg_fwd(WgFwdArgs q) {
+    if (blockIdx.x < q.split) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char wg_lds[];
+        float *red = reinterpret_cast<float *>(wg_lds);
+        const unsigned b = blockIdx.x, plane = q.wgx * q.wgy;
+        wg_block<VW, true, false, 0>(q.w, b % q.wgx, (b % plane) / q.wgx, b / plane, q.wgx, q.wgy, red, red + 4 * (16 * VW) * (16 * VW));
+    } else {
+        const unsigned b = blockIdx.x - q.split;
+        if constexpr (GROUP) fwd_group_block<K, NB, 1, false, 0, 0>(q.f, b % q.fgx, b / q.fgx, q.fgx);
+        else fwd_block<K, NB, 1, false, 0, 0>(q.f, b % q.fgx, b / q.fgx, q.fgx);
+    }
+}
+template <int VW, int K, int NB, bool GROUP> constexpr int wg_fwd_lds_bytes() {
+    constexpr int w = wg_lds_floats<VW>() * (int)sizeof(float), g = GROUP ? group_lds_bytes<K, NB, 1, 0>() : 0;
+    return w > g ? w : g;
 }
 
 // The slab reduction (RArgs and its order of summation: rowlin2.h).
@@ -1043,30 +1094,79 @@ int try_wgrad_mp(const Wgrad &p, hipStream_t s) {
 }
 
 // Two single weight gradients dW_i (o_i, k_i) = G_i^T X_i (no prologue, own workspace each) whose slab reductions the caller launches
-// (r[i]: launch_slab_reduce2).  pair: the two products as ONE launch (k_wg2) where both take the same vector width -- the workgroups of the
-// problem with more rows per workgroup first; otherwise one launch each, as try_wgrad_mp issues them.  Either way every workgroup runs
-// wg_block over the grid of its own problem: the same slabs.  Returns 2 for one launch, 1 for two; 0: a shape or an alignment is not covered,
-// nothing was launched.
+// (r[i]: launch_slab_reduce2).  pair: the two products as ONE launch -- k_wg2 where both take the same vector width, the workgroups of the
+// problem with more rows per workgroup first; k_wg2_roww where problem 0 carries a row weight (problem 0 first, each with its own vector
+// width) -- otherwise one launch each, as try_wgrad_mp issues them.  Either way every workgroup runs wg_block over the grid of its own
+// problem: the same slabs.  Returns 2 for one launch, 1 for two; 0: a shape or an alignment is not covered, nothing was launched.
 template <int MP>
 int try_wgrad_pair_mp(const Wgrad (&p)[2], bool pair, hipStream_t s, RArgs *r) {
     WgSetup u[2];
     for (int i = 0; i < 2; ++i)
-        if (p[i].ng != 1 || p[i].per_gradient || p[i].scale || p[i].roww || !wg_setup(p[i], u[i])) return 0;
+        if (p[i].ng != 1 || p[i].per_gradient || p[i].scale || (i == 1 && p[i].roww) || !wg_setup(p[i], u[i])) return 0;
+    const bool rw = p[0].roww != nullptr;
     r[0] = u[0].r; r[1] = u[1].r;
-    if constexpr (MP == 0) {   // (the paired kernel is built for fp32 operands only: reduced-precision products take one launch each)
-        if (pair && u[0].vw == u[1].vw) {
-            const int first = u[1].a.rows_per_block > u[0].a.rows_per_block ? 1 : 0;
+    if constexpr (MP == 0) {   // (the paired kernels are built for fp32 operands only: reduced-precision products take one launch each)
+        if (pair && (rw ? u[1].vw == 2 : u[0].vw == u[1].vw)) {
+            const int first = !rw && u[1].a.rows_per_block > u[0].a.rows_per_block ? 1 : 0;
             WArgs2 q;
             for (int j = 0; j < 2; ++j) { const WgSetup &v = u[j ? 1 - first : first]; q.a[j] = v.a; q.gx[j] = v.grid.x; q.gy[j] = v.grid.y; }
             q.split = q.gx[0] * q.gy[0];
             const unsigned total = q.split + q.gx[1] * q.gy[1];
-            if (u[0].vw == 4) k_wg2<4, 0><<<total, 256, 0, s>>>(q); else k_wg2<2, 0><<<total, 256, 0, s>>>(q);
+            if (rw) { if (u[0].vw == 4) k_wg2_roww<4, 2, 0><<<total, 256, 0, s>>>(q); else k_wg2_roww<2, 2, 0><<<total, 256, 0, s>>>(q); }
+            else if (u[0].vw == 4) k_wg2<4, 0><<<total, 256, 0, s>>>(q);
+            else k_wg2<2, 0><<<total, 256, 0, s>>>(q);
             return 2;
         }
     }
     for (int i = 0; i < 2; ++i) {
-        if (u[i].vw == 4) k_wg<4, false, false, MP><<<u[i].grid, 256, 0, s>>>(u[i].a); else k_wg<2, false, false, MP><<<u[i].grid, 256, 0, s>>>(u[i].a);
+        if (i == 0 && rw) { if (u[i].vw == 4) k_wg<4, false, true, MP><<<u[i].grid, 256, 0, s>>>(u[i].a); else k_wg<2, false, true, MP><<<u[i].grid, 256, 0, s>>>(u[i].a); }
+        else if (u[i].vw == 4) k_wg<4, false, false, MP><<<u[i].grid, 256, 0, s>>>(u[i].a);
+        else k_wg<2, false, false, MP><<<u[i].grid, 256, 0, s>>>(u[i].a);
     }
+    return 1;
+}
+
+template <int VW, int K, int NB, bool GROUP>
+static bool launch_wg_fwd(const WgFwdArgs &q, unsigned total, hipStream_t s) {
+    constexpr int lds = wg_fwd_lds_bytes<VW, K, NB, GROUP>();
+    static PdfLdsLimit site;
+    if (!pdf_lds_limit_raised(site, reinterpret_cast<const void *>(&k_wg_fwd<VW, K, NB, GROUP>), lds)) return false;
+    k_wg_fwd<VW, K, NB, GROUP><<<total, 256, lds, s>>>(q);
+    return true;
+}
+
+// The grouped weight gradients w (per-gradient inputs: a Bottleneck's five c x c products) and the plain product f (one input, one
+// output, no prologue, statistics or row weight; `accumulate` allowed: the block's gx += dy W1) as ONE launch (k_wg_fwd), followed by the
+// gradients' slab reduction.  Paired are the forms the model's five levels reach: the slab products at K = 32 / 64 beside the VW = 2 / 4
+// gradients, and the group-form products at K = 128 / 256 / 512 beside the VW = 4 gradients; each problem keeps the grid its single launch
+// has (wg_setup; launch_fwd's row blocks, column slabs and choice of form).  Returns 1 when everything was launched; 0 when nothing was
+// (another form, an alignment, a refused LDS limit) -- the caller issues the single launches, which form the same bits.  fp32 operands only.
+template <int MP>
+int try_wgrad_fwd_mp(const Wgrad &w, const Forward &f, hipStream_t s) {
+    static_assert(MP == 0, "the paired kernel is built for fp32 operands only");
+    WgFwdArgs q;
+    WgSetup u;
+    if (!w.per_gradient || f.nin != 1 || f.nout != 1 || f.scale || f.bx || f.roww || f.handoff || f.partial) return 0;
+    if (!wg_setup(w, u) || !fwd_args(f, q.f)) return 0;
+    const int k = f.k, nob = fwd_nob1(k, f.o, false, false);
+    if (!nob) return 0;
+    const int nslabs = f.o / (nob * 16);
+    const int gx = fwd_grid_rows(f.n, nslabs, true);
+    const bool group = k >= 128 && group_form_wanted(q.f, k, nslabs * nob);
+    const int gy = group ? nslabs * nob / GROUP_GN : nslabs;
+    q.w = u.a; q.wgx = u.grid.x; q.wgy = u.grid.y; q.split = u.grid.x * u.grid.y * u.grid.z; q.fgx = (unsigned)gx;
+    const unsigned total = q.split + (unsigned)(gx * gy);
+    bool ok = false;
+    if (group && u.vw == 4) {
+        if (k == 128) ok = launch_wg_fwd<4, 128, GROUP_GN, true>(q, total, s);
+        else if (k == 256) ok = launch_wg_fwd<4, 256, GROUP_GN, true>(q, total, s);
+        else if (k == 512) ok = launch_wg_fwd<4, 512, GROUP_GN, true>(q, total, s);
+    } else if (!group) {
+        if (k == 32 && nob == 2 && u.vw == 2) ok = launch_wg_fwd<2, 32, 2, false>(q, total, s);
+        else if (k == 64 && nob == 4 && u.vw == 4) ok = launch_wg_fwd<4, 64, 4, false>(q, total, s);
+    }
+    if (!ok) return 0;
+    launch_slab_reduce(u.r, w.ng, u.any_bias, s);
     return 1;
 }
 

@@ -482,10 +482,9 @@ static inline void td_wg_plan(long m, int cin, int cout, int *nblk, long *split,
     *ppb = ((m + sp - 1) / sp + 15) / 16 * 16;
     *split = (m + *ppb - 1) / *ppb;
 }
-// scratch floats of the forward: slabs of the two Gram products (pdf_rowlin_wgrad_ws_floats)
+// scratch floats of the forward: slabs of the two Gram products (pdf_rowlin_wgrad_ws_floats), each with its own workspace
 extern "C" long pdf_td_fwd_scratch_floats(long n, int cin) {
-    const long a = pdf_rowlin_wgrad_ws_floats(n, cin, cin, 1), b = pdf_rowlin_wgrad_ws_floats(n, cin, 32, 1);
-    return a > b ? a : b;
+    return pdf_rowlin_wgrad_ws_floats(n, cin, cin, 1) + pdf_rowlin_wgrad_ws_floats(n, cin, 32, 1);   // (one after the other: the two products share a launch)
 }
 // scratch floats of the backward: fake coef (4 cout) | AB (2 cout) | Qp (cin*cin) | QqT (cin*32) | partial (pdf_bn_partial_floats(m, cout))
 // | slabs of the sparse weight gradient (blocks x row ranges x 64 x 64)
@@ -509,9 +508,14 @@ extern "C" int pdf_td_forward(long n, long m, int cin, int cout, void *const *p,
     int rc = 0;
     if (training) {
         if (!p[14]) return PDF_ERR_BAD_ARG;
-        rc = pdf_rowlin_wgrad_roww(n, cin, cin, x, cin, x, cin, gxx, Z + 3, 32, (float *)p[14], mma_input, stream);       // x^T diag(cnt) x (written)
-        if (rc) return rc;
-        rc = pdf_rowlin_wgrad_roww(n, cin, 32, Z, 32, x, cin, gz, nullptr, 0, (float *)p[14], mma_input, stream);        // [R | cnt]^T x
+        // The two Gram products are independent: ONE product launch (rl2::k_wg2_roww; PDFOPS_PAIR=0 or reduced-precision operands: one
+        // each) and ONE two-problem slab reduction, each problem over the grid and the workspace of its single call -- the same bits.
+        PdfWgrad2 w;
+        w.n[0] = n; w.k[0] = cin; w.o[0] = cin; w.g[0] = x; w.x[0] = x; w.dw[0] = gxx; w.db[0] = nullptr; w.ws[0] = (float *)p[14];   // x^T diag(cnt) x (written)
+        w.roww = Z + 3; w.rws = 32;
+        w.n[1] = n; w.k[1] = cin; w.o[1] = 32; w.g[1] = Z; w.x[1] = x; w.dw[1] = gz; w.db[1] = nullptr;                               // [R | cnt]^T x
+        w.ws[1] = (float *)p[14] + pdf_rowlin_wgrad_ws_floats(n, cin, cin, 1);
+        rc = pdf_rowlin_wgrad_pair(w, mma_input, stream);
         if (rc) return rc;
         td::k_td_coef<<<cout, 256, 0, s>>>(cin, cout, (double)m * 16.0, W, consts, gz, gxx, gamma, beta, eps, momentum, (float *)p[8],
                                            (float *)p[9], coef);
